@@ -16,20 +16,32 @@ frame) run on `depth` side streams while earlier batches' MFMA levels run on the
 G batches share one FPS launch and one main-stream pass.  The warm-up fills the pipeline
 (`depth` groups in flight), then the timed window pushes exactly K batches and completes
 exactly K (K a multiple of G): every stage processes K batches of work inside the window.
-The input rotates over 8 distinct device-resident batches, and every output of warm-up,
+The input rotates over 8 distinct device-resident batches; with --full every output of warm-up,
 window and drain is checked bit for bit against one-batch forward() of its batch.
 Synthetic data: uniform [-1, 1]^3 float32 frames (seeded per rank), random-init weights.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run does what the headline needs and nothing else: it builds the inputs and the backbone, fills
+the pipeline, times the window of K steps, writes the last step's outputs (--dump-outputs) and prints the
+line.  --full adds everything else the benchmark measures or checks: the bit-equality check of every
+pipeline output against one-batch forward(), the host-frame, native-fp32-MFMA and standalone legs, the
+other BASELINE configs, the density / variant / voxel / host-frame legs, the CPU baselines and the
+precision check against the oracle (each still has its own --no-... switch under --full).
 With --gpus N > 1 and no torch.distributed.run environment, bench.py starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a CHILD process (before
 anything touches the GPU) and relays its output and exit code; under torch.distributed.run
 (WORLD_SIZE set) every rank checks WORLD_SIZE == --gpus.
 
 Output: the LAST stdout line is a compact JSON record (<= LINE_MAX bytes: the driver keeps only
-the tail of stdout) with the contract keys, the headline roofline, the CPU baseline, the
-precision check and the distributed record; the full record (every kernel's roofline, the
-standalone timings, the density / voxel / host-frame / variant legs) goes to --detail.
+the tail of stdout) with the contract keys, the headline roofline (from the HIP events of the timed
+window itself) and the distributed record, and with --full the CPU baseline and the precision check;
+the full record (every kernel's roofline and, with --full, the standalone timings and the density /
+voxel / host-frame / variant legs) goes to --detail.
+
+--dump-outputs DIR: after the timed window, what its last step returned to the caller (the (B, 1024)
+float32 global features of the last batch the window completed) is written to DIR/global_features.npy
+(rank r > 0 of an N-rank run: DIR/global_features.rank<r>.npy).  Inputs and weights are seeded, so two
+runs with the same arguments write the same array.
 """
 import argparse
 import hashlib
@@ -740,13 +752,26 @@ def main():
     ap.add_argument("--no-density", action="store_true", help="skip the Tier R / variant / voxel / host-frame legs")
     ap.add_argument("--seed-rank", type=int, default=None,
                     help="generate the frames of this rank (a 1-process run reproducing one rank of an N-rank run)")
-    ap.add_argument("--dump", default=None, help="write this rank's output digests to DUMP.rank<r>.json")
+    ap.add_argument("--dump", default=None,
+                    help="write this rank's output digests (of the forward() references: with --full) to "
+                         "DUMP.rank<r>.json")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the global features of "
+                         "the last batch the window completed, float32) to DIR/global_features.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline window: the bit-equality check against forward(), "
+                         "the host-feed / fp32-MFMA / standalone legs, the other configs, the density legs, the CPU "
+                         "baselines and the precision check (a plain run skips them all)")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the one-batch forward() references and the bit-equality check of every pipeline "
                          "output (PMC passes: only the pipeline's own launches are then counted)")
     ap.add_argument("--detail", default=os.path.join(REPO, "gpurun_out", "bench_detail.json"),
                     help="file for the full record (rank 0); the last stdout line is the compact one")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline window alone
+        args.no_verify = args.no_host_feed = args.no_fp32_mfma_leg = args.no_standalone = True
+        args.no_extras = args.no_density = args.no_cpu_baseline = True
 
     if args.hw_queues:
         os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, max(1, args.hw_queues)))
@@ -770,6 +795,7 @@ def main():
     B, N = args.batch, args.points
     G = pick_group(args.steps, args.fps_group)
     digests = {}
+    last_out = {}  # per leg: what the last step of its timed window returned
     local_ms = {}  # this rank's own window time per leg (the line reports the max over ranks)
 
     def measure(key, cfg, dtype, B, N, steps, warmup, depth, G, x3=True, events=True,
@@ -835,12 +861,17 @@ def main():
             assert not bad, f"{key}: streaming outputs differ from forward() for batches {bad[:5]}"
             digests[key] = [hashlib.sha256(r.cpu().numpy().tobytes()).hexdigest() for r in refs]
         local_ms[key] = local * 1e3
+        last_out[key] = win[-1]
         return elapsed, timers.totals(), bb, xs, refs
 
     tot_x3 = None
     pn.FUSE_LAYER1 = not args.no_layer1_fuse
     elapsed, tot, bb, xs, refs = measure("ssg", pn.SSG, "f32", B, N, args.steps, args.warmup, args.depth, G,
                                          x3=bool(args.x3))
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "global_features" + (f".rank{rank}" if rank else "") + ".npy"
+        np.save(os.path.join(args.dump_outputs, name), last_out["ssg"].cpu().numpy().astype(np.float32, copy=False))
     host_feed = None
     if not args.no_host_feed:
         # the same workload entering as host NumPy frames (PCIe-inclusive: pinned staging by host threads,

@@ -114,7 +114,9 @@ def test_launch_ranks_starts_n_ranks(tmp_path):
     exit code returned (a stand-in script: this container has no GPU)."""
     script = tmp_path / "rank.py"
     script.write_text("import os, sys\n"
-                      "print('rank', os.environ['RANK'], 'of', os.environ['WORLD_SIZE'], sys.argv[1:], flush=True)\n"
+                      # one write per rank: the ranks share the pipe, and a print of several pieces interleaves
+                      "sys.stdout.write('rank %s of %s %s\\n' % (os.environ['RANK'], os.environ['WORLD_SIZE'], sys.argv[1:]))\n"
+                      "sys.stdout.flush()\n"
                       "sys.exit(3 if os.environ['RANK'] == '1' and '--fail' in sys.argv else 0)\n")
     code = ("import sys; sys.path.insert(0, %r); import bench; "
             "sys.exit(bench.launch_ranks(2, sys.argv[1:], script=%r))" % (REPO, str(script)))
@@ -125,6 +127,12 @@ def test_launch_ranks_starts_n_ranks(tmp_path):
     assert got == ["rank 0 of 2 ['--x', '1']", "rank 1 of 2 ['--x', '1']"]
     r = subprocess.run([sys.executable, "-c", code, "--fail"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode != 0
+
+
+def test_full_and_dump_outputs_are_options():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
 
 
 def test_world_size_must_match_gpus():

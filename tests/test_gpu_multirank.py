@@ -1,7 +1,7 @@
 """bench.py's N-rank path rehearsed on one GPU (the driver's 8-GPU scaling run uses the same code).
 
-Plain `bench.py --gpus 2` (the driver's form) starts a child torch.distributed.run with two ranks
-before any GPU call; with more ranks than visible devices they share the GPU and use gloo for the
+`bench.py --gpus 2` (the driver's form; here with --full, whose forward() references give the output
+digests) starts a child torch.distributed.run with two ranks before any GPU call; with more ranks than visible devices they share the GPU and use gloo for the
 timing collectives (RCCL needs a device per rank).  Each
 rank processes the frames of its own seed; the test then runs each rank's workload alone
 (`--seed-rank r`) and requires bit-identical outputs, and checks that the aggregate rate counts
@@ -17,7 +17,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--points", "8192", "--batch", "4", "--steps", "6", "--warmup", "1", "--rotate", "3", "--no-extras",
+ARGS = ["--full", "--points", "8192", "--batch", "4", "--steps", "6", "--warmup", "1", "--rotate", "3", "--no-extras",
         "--no-density", "--no-cpu-baseline", "--no-fp32-mfma-leg", "--no-standalone"]
 
 
@@ -58,7 +58,7 @@ def test_bench_two_ranks_on_one_gpu(cuda, tmp_path):
     assert json.load(open(tmp_path / "w2.rank0.json"))["digests"] != json.load(open(tmp_path / "w2.rank1.json"))["digests"]
 
 
-ARGS_C3 = ["--batch", "32", "--points", "65536", "--steps", "4", "--warmup", "1", "--rotate", "4", "--no-extras",
+ARGS_C3 = ["--full", "--batch", "32", "--points", "65536", "--steps", "4", "--warmup", "1", "--rotate", "4", "--no-extras",
            "--no-density", "--no-cpu-baseline", "--no-fp32-mfma-leg", "--no-standalone"]
 
 
@@ -100,7 +100,7 @@ def test_bench_configs3_eight_ranks_on_one_gpu(cuda, tmp_path):
     assert json.load(open(tmp_path / "w8.rank0.json"))["digests"] != json.load(open(tmp_path / "w8.rank7.json"))["digests"]
 
 
-ARGS_C4 = ["--batch", "4", "--points", "8192", "--steps", "3", "--warmup", "1", "--rotate", "2", "--msg-batch", "32",
+ARGS_C4 = ["--full", "--batch", "4", "--points", "8192", "--steps", "3", "--warmup", "1", "--rotate", "2", "--msg-batch", "32",
            "--msg-steps", "3", "--no-density", "--no-cpu-baseline", "--no-fp32-mfma-leg", "--no-standalone",
            "--no-host-feed"]
 

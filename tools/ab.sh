@@ -11,7 +11,7 @@
 # Each arm's full record lands in OUTDIR/armI_REP.detail.json; a one-line summary is printed.
 set -o pipefail
 TESTK=""; CAND=""
-BASE="--no-extras --no-density --no-cpu-baseline --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
+BASE="--full --no-extras --no-density --no-cpu-baseline --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
 while getopts "t:c:b:" opt; do
   case $opt in
     t) TESTK=$OPTARG ;;

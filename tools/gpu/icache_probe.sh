@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 60 rocprofv3 --list-avail > $O/avail.txt 2>&1 || true
 grep -i "SQC_ICACHE\|SQC_INST\|SQ_IFETCH" $O/avail.txt | head -20 > $O/avail_icache.txt || true
-ARGS="--no-verify --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
+ARGS="--full --no-verify --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
 for w in none fps; do
   timeout -s KILL 240 rocprofv3 --kernel-trace --pmc SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH \
       --output-format csv -d $O/$w -o p -- python3 $R/tools/skip_probe.py $w $ARGS > $O/$w.json 2> $O/$w.err || exit 11

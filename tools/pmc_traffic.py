@@ -3,7 +3,7 @@
 Input: the FETCH_SIZE and WRITE_SIZE counter CSVs of `tools/profile_round.sh` (one pass per
 counter, `--kernel-trace` only beside `--pmc`) plus its calibration passes (a 1 GiB device copy),
 and the bench line each pass printed (its `pipeline.frames_per_launch` F).  The passes run
-`bench.py --no-verify` at the driver's settings (--steps 20: G = 4 batches of 32 frames, 128-frame
+`bench.py --full --no-verify` at the driver's settings (--steps 20: G = 4 batches of 32 frames, 128-frame
 launches), so every library launch is a pipeline launch of F frames: the one-batch forward()
 references that the timed bench compares against are not issued.
 

@@ -22,16 +22,16 @@ mkdir -p $O
 cd $R
 # the PMC passes run the driver's shape (--steps 20: G = 4, 128-frame launches) with only the pipeline's own
 # launches (--no-verify: no one-batch forward() references), so every counted dispatch is a 128-frame launch
-SHORT="--no-verify --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
+SHORT="--full --no-verify --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone --steps 20 --warmup 5"
 if [ "${2:-tests}" = "tests" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/tests.log 2>&1 || exit 11
 fi
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || exit 12
-timeout -k 10 600 python bench.py --steps 240 --warmup 3 --no-extras --no-density --no-fp32-mfma-leg \
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || exit 12
+timeout -k 10 600 python bench.py --full --steps 240 --warmup 3 --no-extras --no-density --no-fp32-mfma-leg \
     --detail $O/bench240_detail.json > $O/bench240.json 2> $O/bench240.err || exit 19
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o prof -- \
-    python3 $R/bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone \
+    python3 $R/bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-density --no-fp32-mfma-leg --no-standalone \
     --detail $O/prof_bench_detail.json > $O/prof_bench.json 2> $O/prof.err || exit 13
 timeout -s KILL 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_calib_f -o c -- \
     python3 $R/tools/pmc_calib.py > $O/pmc_calib.log 2>&1 || exit 14
