@@ -255,16 +255,32 @@ MLP16_SHAPES = {(True, 64, 64, 128, 32), (True, 32, 32, 64, 16), (True, 64, 96, 
                 (False, 128, 128, 256, 128), (False, 64, 64, 128, 32)}
 
 
+_PACKERS = {"16": ("lidar_mlp_packed_size16", "lidar_mlp_pack16_f32", np.float32),
+            "x3": ("lidar_mlp_packed_size_x3", "lidar_mlp_pack_x3_f32", np.uint8),
+            "x1": ("lidar_mlp_packed_size_x1", "lidar_mlp_pack_x1_f32", np.uint8)}
+
+
+# per arithmetic of a fused-kernel branch: (the image's key in the branch entry, its _PACKERS kind)
+_IMAGE = {"x1": ("packed_x1", "x1"), "x3": ("packed_x3", "x3"), "f32": ("packed16", "16")}
+
+
+def _pack_branch(kind, layers, xyz_level=None):
+    """Host-side packed image of a branch's three layers for the fused kernel of `kind` (_PACKERS: the
+    library's size and pack calls and the image's dtype; the x1 calls take no xyz_level)."""
+    size, pack, dtype = _PACKERS[kind]
+    (w1, _), (w2, _), (w3, _) = layers
+    dims = ([] if kind == "x1" else [int(xyz_level)]) + [w1.shape[1], w2.shape[1], w3.shape[1]]
+    lib = nat.load_library()
+    out = np.zeros(getattr(lib, size)(*dims), dtype=dtype)
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for layer in layers for a in layer]
+    nat.check(getattr(lib, pack)(*dims, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs],
+                                 out.ctypes.data_as(ctypes.c_void_p)), pack)
+    return out
+
+
 def pack_branch16(layers, xyz_level):
     """Host-side packed image for lidar_sa_group_mlp16_f32 (16x16x4 MFMA fragments)."""
-    (w1, b1), (w2, b2), (w3, b3) = layers
-    c1, c2, c3 = w1.shape[1], w2.shape[1], w3.shape[1]
-    lib = nat.load_library()
-    out = np.zeros(lib.lidar_mlp_packed_size16(int(xyz_level), c1, c2, c3), dtype=np.float32)
-    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
-    nat.check(lib.lidar_mlp_pack16_f32(int(xyz_level), c1, c2, c3, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs],
-                                       out.ctypes.data_as(ctypes.c_void_p)), "lidar_mlp_pack16_f32")
-    return out
+    return _pack_branch("16", layers, xyz_level)
 
 
 def group_mlp16(p, q, idx, n, packed, widths, out, out_offset=0, xyz_level=False):
@@ -290,27 +306,13 @@ def group_mlp16(p, q, idx, n, packed, widths, out, out_offset=0, xyz_level=False
 def pack_branch_x3(layers, xyz_level):
     """Host-side packed image (uint8) for lidar_sa_group_mlp_x3_f32 (fp16 hi/lo fragments of each layer's
     W 2^s, h3 arithmetic; csrc/h3.hpp)."""
-    (w1, b1), (w2, b2), (w3, b3) = layers
-    c1, c2, c3 = w1.shape[1], w2.shape[1], w3.shape[1]
-    lib = nat.load_library()
-    out = np.zeros(lib.lidar_mlp_packed_size_x3(int(xyz_level), c1, c2, c3), dtype=np.uint8)
-    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
-    nat.check(lib.lidar_mlp_pack_x3_f32(int(xyz_level), c1, c2, c3, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs],
-                                        out.ctypes.data_as(ctypes.c_void_p)), "lidar_mlp_pack_x3_f32")
-    return out
+    return _pack_branch("x3", layers, xyz_level)
 
 
 def pack_branch_x1(layers):
     """Host-side packed image (uint8) for lidar_sa_group_mlp_x1_f32 (bf16 spec: bf16-rounded
     W1 xyz rows, hi fragments of W2 / W3, fp32 biases)."""
-    (w1, b1), (w2, b2), (w3, b3) = layers
-    c1, c2, c3 = w1.shape[1], w2.shape[1], w3.shape[1]
-    lib = nat.load_library()
-    out = np.zeros(lib.lidar_mlp_packed_size_x1(c1, c2, c3), dtype=np.uint8)
-    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (w1, b1, w2, b2, w3, b3)]
-    nat.check(lib.lidar_mlp_pack_x1_f32(c1, c2, c3, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs],
-                                        out.ctypes.data_as(ctypes.c_void_p)), "lidar_mlp_pack_x1_f32")
-    return out
+    return _pack_branch("x1", layers)
 
 
 def group_mlp_x1(p, idx, n, packed, widths, out, out_offset=0, xyz=None, centres=None):
@@ -409,32 +411,57 @@ def group_mlp_bq(xyz, centres, grid, radius, nsample, packed, widths, out, out_o
     return out
 
 
+def _kpad(cfeat):
+    """Width of a level's padded input rows [f (cfeat), x, y, z, 0-pad]: k padded to 16."""
+    return (cfeat + 3 + 15) // 16 * 16
+
+
+def pad_layer(w, b, kin):
+    """(W (cin, c), b) of a later layer -> (wp (kin, cp), bp (cp,)) float32: rows zero-padded to kin (the
+    previous layer's padded width), columns and bias to a multiple of 128 (the dense kernel's tile)."""
+    w = np.asarray(w, np.float32)
+    cin, c = w.shape
+    cp = (c + 127) // 128 * 128
+    wp = np.zeros((kin, cp), np.float32)
+    wp[:cin, :c] = w
+    bp = np.zeros(cp, np.float32)
+    bp[:c] = b
+    return wp, bp
+
+
+def layer1_layout(w, b, cfeat, xyz_rows=True):
+    """(W1 (3 + cfeat, c), b1) -> (wp (kp, cp), bp (cp,)) in the physical row order every GEMM here
+    reads: canonical rows [x, y, z, f...] become [f..., x, y, z, 0-pad] (k padded to 16), columns and
+    bias zero-padded to a multiple of 128.  xyz_rows=False leaves the three xyz rows zero (the bf16
+    spec's W1_f: the offsets' part runs per grouped row)."""
+    w = np.asarray(w, np.float32)
+    wp, bp = pad_layer(w[3:], b, _kpad(cfeat))
+    if xyz_rows:
+        wp[cfeat:cfeat + 3, :w.shape[1]] = w[:3]
+    return wp, bp
+
+
+def mlp_layout(layers, cfeat):
+    """[(wp, bp)] of a whole MLP: layer1_layout, then every later layer's rows padded to the columns
+    of the one before it."""
+    out = [layer1_layout(*layers[0], cfeat)]
+    for w, b in layers[1:]:
+        out.append(pad_layer(w, b, out[-1][0].shape[1]))
+    return out
+
+
 def generic_branch_weights(layers, cfeat, to_dev, arith):
-    """Dense-GEMM operands of an SA branch of any shape (sa_branch_generic): layer 1's rows reordered
-    from the canonical [x, y, z, f...] to the grouped rows' [f..., x, y, z, 0-pad] (k padded to 16),
-    every layer's columns (and the next layer's rows) zero-padded to a multiple of 128.  arith: "x3"
-    (h3 images), "x1" (bf16-spec images) or "f32" (the native fp32 GEMM's plain weights)."""
-    kp = (cfeat + 3 + 15) // 16 * 16
-    out = {"k": kp, "layers": [], "c3": layers[-1][0].shape[1], "arith": arith}
-    kin = kp
-    for li, (w, b) in enumerate(layers):
-        w = np.asarray(w, np.float32)
-        cin, c = w.shape
-        cp = (c + 127) // 128 * 128
-        wp = np.zeros((kin, cp), np.float32)
-        if li == 0:
-            wp[:cfeat, :c] = w[3:]
-            wp[cfeat:cfeat + 3, :c] = w[:3]
-        else:
-            wp[:cin, :c] = w
-        bp = np.zeros(cp, np.float32)
-        bp[:c] = b
+    """Dense-GEMM operands of an SA branch of any shape (sa_branch_generic), in mlp_layout: layer 1's
+    rows in the grouped rows' order [f..., x, y, z, 0-pad], every layer's columns (and the next layer's
+    rows) zero-padded to a multiple of 128.  arith: "x3" (h3 images), "x1" (bf16-spec images) or "f32"
+    (the native fp32 GEMM's plain weights)."""
+    out = {"k": _kpad(cfeat), "layers": [], "c3": layers[-1][0].shape[1], "arith": arith}
+    for wp, bp in mlp_layout(layers, cfeat):
         wd = to_dev(wp)
-        lay = {"w": wd, "b": to_dev(bp), "cout": cp}
+        lay = {"w": wd, "b": to_dev(bp), "cout": wp.shape[1]}
         if arith != "f32":
             lay["packed"] = pack_dense_x3(wd, x1=arith == "x1")
         out["layers"].append(lay)
-        kin = cp
     return out
 
 
@@ -490,17 +517,9 @@ def layer1_weights(layer, cfeat, to_dev):
     w1 rows [f..., x, y, z, 0-pad] (k padded to 16), wq rows [x, y, z, 0-pad] (16), columns
     zero-padded to a multiple of 128 (the dense kernel's tile)."""
     w1, b1 = layer
-    c1 = w1.shape[1]
-    kp = (cfeat + 3 + 15) // 16 * 16
-    cp = (c1 + 127) // 128 * 128
-    w1p = np.zeros((kp, cp), np.float32)
-    w1p[:cfeat, :c1] = w1[3:]
-    w1p[cfeat:cfeat + 3, :c1] = w1[:3]
-    wq = np.zeros((16, cp), np.float32)
-    wq[:3, :c1] = w1[:3]
-    bp = np.zeros(cp, np.float32)
-    bp[:c1] = b1
-    return {"w1": to_dev(w1p), "b1": to_dev(bp), "wq": to_dev(wq), "zero": to_dev(np.zeros(cp, np.float32))}
+    w1p, bp = layer1_layout(w1, b1, cfeat)
+    wq, _ = pad_layer(w1[:3], b1, 16)
+    return {"w1": to_dev(w1p), "b1": to_dev(bp), "wq": to_dev(wq), "zero": to_dev(np.zeros_like(bp))}
 
 
 def centre_layer1(new_xyz, branches, out=None, slot=0):
@@ -680,6 +699,11 @@ def _call(timers, name, frames, fn, *a, **k):
     return timers(name, frames, fn, *a, **k) if timers is not None else fn(*a, **k)
 
 
+def _tag(li, lvl, bi):
+    """A branch's launch-tag prefix (the timers' keys): sa<level>, and _b<branch> on a multi-branch level."""
+    return f"sa{li + 1}" + (f"_b{bi}" if len(lvl["branches"]) > 1 else "")
+
+
 class PointNet2Backbone:
     """SSG / MSG PointNet++ encoder on liblidar_amd.  ``forward(xyz)`` -> global feature
     (B, C_last) plus, with keep_levels, per level (new_xyz, features, fps_idx, [ball-query
@@ -713,67 +737,57 @@ class PointNet2Backbone:
         cfeat = 0
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
         for lvl, wl in zip(cfg["levels"], self.weights):
-            kp = (cfeat + 3 + 15) // 16 * 16
             if lvl.get("group_all"):
-                (w1, b1), (w2, b2), (w3, b3) = wl[0]
-                # canonical rows [x, y, z, f...] -> physical input [f..., x, y, z, 0-pad]; every
-                # width zero-padded to the GEMM's 128 columns (and the next layer's rows)
-                cp = [(w.shape[1] + 127) // 128 * 128 for w in (w1, w2, w3)]
-                w1p = np.zeros((kp, cp[0]), np.float32)
-                w1p[:cfeat, :w1.shape[1]] = w1[3:]
-                w1p[cfeat:cfeat + 3, :w1.shape[1]] = w1[:3]
-                w2p = np.zeros((cp[0], cp[1]), np.float32)
-                w2p[:w2.shape[0], :w2.shape[1]] = w2
-                w3p = np.zeros((cp[1], cp[2]), np.float32)
-                w3p[:w3.shape[0], :w3.shape[1]] = w3
-                bp = [np.pad(np.asarray(bb_, np.float32), (0, c - len(bb_))) for bb_, c in zip((b1, b2, b3), cp)]
-                entry = {"group_all": True, "k": kp, "cfeat": cfeat, "cout": w3.shape[1],
-                         "w": [t(w1p), t(w2p), t(w3p)], "b": [t(v) for v in bp]}
-                if self.x3:  # packed once into x3 B fragments
-                    entry["w_x3"] = [pack_dense_x3(w) for w in entry["w"]]
-                    entry["h3_bounds"] = [h3_bounds(w1p, bp[0]), h3_bounds(w2p, bp[1]), h3_bounds(w3p, bp[2])]
-                self.levels.append(entry)
-                cfeat = w3.shape[1]
+                self.levels.append(self._build_group_all(wl[0], cfeat, t))
+                cfeat = self.levels[-1]["cout"]
                 continue
-            xyz_level = cfeat == 0
-            branches = []
-            for (r, ns, widths, layers) in zip(lvl["radii"], lvl["nsamples"], lvl["mlps"], wl):
-                br = {"r": r, "ns": ns, "widths": widths}
-                if (xyz_level, *widths, ns) not in MLP16_SHAPES:
-                    # no fused kernel for this shape: grouped rows in HBM + the dense GEMMs (sa_branch_generic)
-                    arith = "x1" if self.bf16 else ("x3" if x3 else "f32")
-                    br["generic"] = generic_branch_weights(layers, cfeat, t, arith)
-                elif self.bf16:
-                    br["packed_x1"] = torch.from_numpy(pack_branch_x1(layers)).to(self.device)
-                    if not xyz_level:  # W1_f: rows [f..., (x, y, z) = 0, 0-pad], columns to 128
-                        w1, b1 = layers[0]
-                        cp = (w1.shape[1] + 127) // 128 * 128
-                        w1f = np.zeros((kp, cp), np.float32)
-                        w1f[:cfeat, :w1.shape[1]] = w1[3:]
-                        b1p = np.zeros(cp, np.float32)
-                        b1p[:w1.shape[1]] = b1
-                        br["pre_x1"] = {"w1f": t(w1f), "b1": t(b1p)}
-                        br["pre_x1"]["w1f_x1"] = pack_dense_x3(br["pre_x1"]["w1f"], x1=True)
-                else:
-                    if x3:
-                        br["packed_x3"] = torch.from_numpy(pack_branch_x3(layers, xyz_level)).to(self.device)
-                    else:
-                        br["packed16"] = torch.from_numpy(pack_branch16(layers, xyz_level)).to(self.device)
-                    if not xyz_level:
-                        br["pre"] = layer1_weights(layers[0], cfeat, t)
-                        if x3:
-                            br["pre"]["w1_x3"] = pack_dense_x3(br["pre"]["w1"])
-                            br["pre"]["wq_x3"] = pack_dense_x3(br["pre"]["wq"])
-                branches.append(br)
+            branches = [self._build_branch(r, ns, widths, layers, cfeat, t)
+                        for r, ns, widths, layers in zip(lvl["radii"], lvl["nsamples"], lvl["mlps"], wl)]
             entry = {"div": lvl["npoint_div"], "branches": branches, "cfeat": cfeat}
-            if not xyz_level:  # the previous level writes this level's padded rows [f, x, y, z, 0]
-                entry.update(pre=True, k=kp)
+            if cfeat:  # the previous level writes this level's padded rows [f, x, y, z, 0]
+                entry.update(pre=True, k=_kpad(cfeat))
                 if self.bf16 and FUSE_LAYER1 and all("pre_x1" in br for br in branches):
                     entry["pre_x1_cat"] = fused_layer1_x1(branches)  # one layer-1 GEMM for every branch
             self.levels.append(entry)
             cfeat = sum(w[-1] for w in lvl["mlps"])
         self.out_channels = cfeat
         self.timers = None  # set to a _Timers() to time every launch
+
+    def _build_group_all(self, layers, cfeat, t):
+        """The group_all level's entry: its MLP in mlp_layout (the dense GEMMs' operands) and, for the
+        h3 chain, the packed x3 B fragments and each layer's exponent bounds."""
+        lay = mlp_layout(layers, cfeat)
+        entry = {"group_all": True, "k": _kpad(cfeat), "cfeat": cfeat, "cout": layers[-1][0].shape[1],
+                 "w": [t(w) for w, _ in lay], "b": [t(b) for _, b in lay]}
+        if self.x3:  # packed once into x3 B fragments
+            entry["w_x3"] = [pack_dense_x3(w) for w in entry["w"]]
+            entry["h3_bounds"] = [h3_bounds(w, b) for w, b in lay]
+        return entry
+
+    def _build_branch(self, r, ns, widths, layers, cfeat, t):
+        """One SA branch's entry.  "kind", decided here once, is what forward() switches on: "x1" (bf16
+        spec), "x3" (h3) or "f32" (native fp32) — the fused kernel of that arithmetic, its image under
+        "packed_x1" / "packed_x3" / "packed16" and, on a feature level, the per-point layer-1 operands
+        under "pre_x1" / "pre" — or "generic": no fused kernel for this shape, grouped rows in HBM + the
+        dense GEMMs of the same arithmetic (sa_branch_generic)."""
+        xyz_level = cfeat == 0
+        arith = "x1" if self.bf16 else ("x3" if self.x3 else "f32")
+        br = {"r": r, "ns": ns, "widths": widths, "kind": arith}
+        if (xyz_level, *widths, ns) not in MLP16_SHAPES:
+            br.update(kind="generic", generic=generic_branch_weights(layers, cfeat, t, arith))
+            return br
+        key, pk = _IMAGE[arith]
+        br[key] = torch.from_numpy(_pack_branch(pk, layers, xyz_level)).to(self.device)
+        if not xyz_level and arith == "x1":  # W1_f: rows [f..., (x, y, z) = 0, 0-pad], columns to 128
+            w1f, b1 = layer1_layout(*layers[0], cfeat, xyz_rows=False)
+            br["pre_x1"] = {"w1f": t(w1f), "b1": t(b1)}
+            br["pre_x1"]["w1f_x1"] = pack_dense_x3(br["pre_x1"]["w1f"], x1=True)
+        elif not xyz_level:
+            br["pre"] = layer1_weights(layers[0], cfeat, t)
+            if arith == "x3":
+                br["pre"]["w1_x3"] = pack_dense_x3(br["pre"]["w1"])
+                br["pre"]["wq_x3"] = pack_dense_x3(br["pre"]["wq"])
+        return br
 
     def _grid_buffer(self, B, N, device):
         """The ball-query grid buffer forward() bins xyz levels into (grown on demand, reused by
@@ -825,8 +839,8 @@ class PointNet2Backbone:
             R = (B * M + 127) // 128 * 128 if padded else B * M
             out_rows = torch.empty((R, stride), dtype=torch.float32, device=xyz.device)
             out = out_rows[:B * M].view(B, M, stride)
-            pq = None  # per-point layer 1 of the fused branches: {branch index: rows}
-            fb = [i for i, br in enumerate(lvl["branches"]) if "generic" not in br]
+            pq = {}  # per-point layer 1 of the fused-kernel branches: {branch index: rows}
+            fb = [i for i, br in enumerate(lvl["branches"]) if br["kind"] != "generic"]
             if lvl.get("pre") and fb:
                 fbr = [lvl["branches"][i] for i in fb]
                 if self.bf16:
@@ -837,66 +851,50 @@ class PointNet2Backbone:
                     res = _call(t, f"sa{li + 1}_layer1_points", B, layer1_per_point, rows, xyz, lvl["cfeat"],
                                 new_xyz, fbr, x3=self.x3)
                 pq = dict(zip(fb, res))
-            off = 0
-            gidxs = []
+            off, gidxs = 0, []
             for bi_, br in enumerate(lvl["branches"]):
-                tag = f"sa{li + 1}" + (f"_b{bi_}" if len(lvl["branches"]) > 1 else "")
-                # work done elsewhere for this branch (StreamingSSG's side streams): its ball-query
-                # indices, or the binning of its frames (None per branch: not done)
-                pb = pl["bq"][bi_] if pl.get("bq") is not None else None
-                pg = pl["grid"][bi_] if pl.get("grid") is not None else None
-                if "generic" in br:
-                    if pb is not None:
-                        gidx = pb
-                    else:
-                        gidx = _call(t, f"{tag}_ball_query", B, ball_query, br["r"], br["ns"], xyz, new_xyz,
-                                     grid=pg)
-                    gidxs.append(gidx)
-                    _call(t, f"{tag}_group_mlp", B, sa_branch_generic, feats, lvl["cfeat"], xyz, new_xyz, gidx,
-                          br["generic"], out, off)
-                    off += br["widths"][-1]
-                    continue
-                fused = pq is None and pb is None and (self.bf16 or "packed_x3" in br) and (
-                    pg is not None or N >= BQ_GRID_MIN_N)
-                if fused:
-                    # xyz level: the MLP kernel answers the ball queries from the frame's grid
-                    if pg is not None:
-                        grid = pg
-                    else:
-                        grid = _call(t, f"{tag}_bq_bin", B, ball_query_bin, br["r"], br["ns"], xyz,
-                                     self._grid_buffer(B, N, xyz.device))
-                    gidx = (torch.empty((B, M, br["ns"]), dtype=torch.int32, device=xyz.device)
-                            if keep_levels else None)
-                    _call(t, f"{tag}_group_mlp", B, group_mlp_bq, xyz, new_xyz, grid, br["r"], br["ns"],
-                          br["packed_x1"] if self.bf16 else br["packed_x3"], br["widths"], out=out, out_offset=off,
-                          x1=self.bf16, out_idx=gidx)
-                    gidxs.append(gidx)
-                    off += br["widths"][-1]
-                    continue
-                if pb is not None:
-                    gidx = pb
-                else:
-                    gidx = _call(t, f"{tag}_ball_query", B, ball_query, br["r"], br["ns"], xyz, new_xyz, grid=pg)
-                gidxs.append(gidx)
-                if self.bf16:
-                    if pq is not None:
-                        _call(t, f"{tag}_group_mlp", B, group_mlp_x1, pq[bi_], gidx, N, br["packed_x1"],
-                              br["widths"], out=out, out_offset=off, xyz=xyz, centres=new_xyz)
-                    else:
-                        _call(t, f"{tag}_group_mlp", B, group_mlp_x1, xyz, gidx, N, br["packed_x1"],
-                              br["widths"], out=out, out_offset=off, centres=new_xyz)
-                else:
-                    p16, q16 = (pq[bi_] if pq is not None else (xyz, new_xyz))
-                    kern = group_mlp_x3 if "packed_x3" in br else group_mlp16
-                    _call(t, f"{tag}_group_mlp", B, kern, p16, q16, gidx, N,
-                          br["packed_x3"] if "packed_x3" in br else br["packed16"], br["widths"], out=out,
-                          out_offset=off, xyz_level=pq is None)
+                gidxs.append(self._branch(li, bi_, xyz, new_xyz, feats, pq.get(bi_), out, off, pl, keep_levels))
                 off += br["widths"][-1]
             if keep_levels:
                 out_levels.append((new_xyz, out[..., :ctot], idx, gidxs))
             xyz, feats, rows = new_xyz, (out[..., :ctot] if padded else out), out_rows
             N = M
         return feats, out_levels
+
+    def _branch(self, li, bi, xyz, new_xyz, feats, pq, out, off, pl, keep_levels):
+        """Branch bi of level li into out[..., off:off + c3]; returns its ball-query indices (None when
+        the MLP kernel answered its own queries and keep_levels is off).  pq: the branch's per-point
+        layer-1 rows (a fused-kernel branch of a feature level), else None; pl: forward()'s pre[li]."""
+        t = self.timers
+        B, N, _ = xyz.shape
+        lvl = self.levels[li]
+        br, tag = lvl["branches"][bi], _tag(li, lvl, bi)
+        kind, r, ns, widths = br["kind"], br["r"], br["ns"], br["widths"]
+        # work done elsewhere for this branch (StreamingSSG's side streams): its ball-query
+        # indices, or the binning of its frames (None per branch: not done)
+        pb = pl["bq"][bi] if pl.get("bq") is not None else None
+        pg = pl["grid"][bi] if pl.get("grid") is not None else None
+        if kind in ("x1", "x3") and pq is None and pb is None and (pg is not None or N >= BQ_GRID_MIN_N):
+            # xyz level: the MLP kernel answers the ball queries from the frame's grid
+            if pg is None:
+                pg = _call(t, f"{tag}_bq_bin", B, ball_query_bin, r, ns, xyz, self._grid_buffer(B, N, xyz.device))
+            gidx = (torch.empty((B, new_xyz.shape[1], ns), dtype=torch.int32, device=xyz.device)
+                    if keep_levels else None)
+            _call(t, f"{tag}_group_mlp", B, group_mlp_bq, xyz, new_xyz, pg, r, ns, br[_IMAGE[kind][0]], widths,
+                  out=out, out_offset=off, x1=kind == "x1", out_idx=gidx)
+            return gidx
+        gidx = pb if pb is not None else _call(t, f"{tag}_ball_query", B, ball_query, r, ns, xyz, new_xyz, grid=pg)
+        if kind == "generic":
+            _call(t, f"{tag}_group_mlp", B, sa_branch_generic, feats, lvl["cfeat"], xyz, new_xyz, gidx,
+                  br["generic"], out, off)
+        elif kind == "x1":  # a feature level reads the per-point layer-1 rows, and the points beside them
+            _call(t, f"{tag}_group_mlp", B, group_mlp_x1, pq if pq is not None else xyz, gidx, N, br["packed_x1"],
+                  widths, out=out, out_offset=off, xyz=xyz if pq is not None else None, centres=new_xyz)
+        else:
+            p16, q16 = pq if pq is not None else (xyz, new_xyz)
+            _call(t, f"{tag}_group_mlp", B, group_mlp_x3 if kind == "x3" else group_mlp16, p16, q16, gidx, N,
+                  br[_IMAGE[kind][0]], widths, out=out, out_offset=off, xyz_level=pq is None)
+        return gidx
 
     def _group_all(self, xyz, feats, lvl, rows=None):
         B, M, _ = xyz.shape
@@ -921,12 +919,6 @@ class PointNet2Backbone:
             M, rows = mp, B * mp
         t = self.timers
         ws, bs = lvl["w"], lvl["b"]
-        if self.x3 and not hasattr(nat.load_library(), "lidar_dense_h3p_f32"):
-            # an earlier round's library (A/B through LIDAR_AMD_LIB): fp32 rows between the layers
-            wp = lvl["w_x3"]
-            h1 = _call(t, "sa3_dense1", B, dense_x3s, x2, wp[0], bs[0], ws[0].shape[1])
-            h2 = _call(t, "sa3_dense2", B, dense_x3s, h1, wp[1], bs[1], ws[1].shape[1])
-            return _call(t, "sa3_dense3_pool", B, dense_x3s, h2, wp[2], bs[2], ws[2].shape[1], pool_rows=M)
         if self.x3:  # h3 planes between the layers (split once, by the producer); dense3 fuses the max-pool
             wp, bd = lvl["w_x3"], lvl["h3_bounds"]
             h1, e1 = _call(t, "sa3_dense1", B, dense_h3p, x2, None, wp[0], bs[0], ws[0].shape[1], 1, bd[0])
@@ -941,6 +933,29 @@ class PointNet2Backbone:
 
 
 # ------------------------------------------------------------------ streaming executor
+class _Slot:
+    """One staging slot of StreamingSSG: the group's frames, what a side stream computes from them, and the
+    two events of the hand-off.  levels: per side-stream level (StreamingSSG.side) forward()'s `pre`
+    entry over the slot's G*B frames — {"fps": (idx, centroids, first_zero), "bq": [ball-query indices
+    per branch] or None, "grid": [ball_query_bin buffer per branch] or None}."""
+
+    def __init__(self, stage, levels, main):
+        self.stage = stage  # (G*B, N, 3); with G = 1 allocated once a host batch needs it (StreamingSSG._stage)
+        self.staged = stage is not None  # the slot's group lives in stage (else in the caller's batch)
+        self.levels = levels
+        self.fps_done = torch.cuda.Event()  # recorded by the side stream behind the group's work
+        self.slot_free = torch.cuda.Event()  # recorded by the main stream behind the pass that read the slot
+        self.slot_free.record(main)
+
+    def pre(self, g, clone=False):
+        """forward()'s `pre` mapping for the slot's first g frames: views, or with clone copies (made on
+        the current stream).  The grids cover whole frames and are read in place."""
+        cut = (lambda a: a[:g].clone()) if clone else (lambda a: a[:g])
+        return {li: {"fps": tuple(cut(a) for a in lv["fps"]),
+                     "bq": [cut(a) for a in lv["bq"]] if lv["bq"] is not None else None, "grid": lv["grid"]}
+                for li, lv in enumerate(self.levels)}
+
+
 class StreamingSSG:
     """Frame-batch pipeline for a continuous feed (SSG/MSG backbone).
 
@@ -989,8 +1004,6 @@ class StreamingSSG:
             raise ValueError("StreamingSSG: bq must be 'side', 'bin' or 'main'")
         self.bq = bq
         dev = backbone.device
-        lvl0 = backbone.levels[0]
-        self.M1 = max(1, n // lvl0["div"])
         # side_priority < 0 puts the latency-bound FPS chains ahead of the MLP waves in the
         # dispatcher (HIP stream priority); results do not depend on it
         # the process's shared side streams: a pipeline created after another keeps its queues
@@ -1001,29 +1014,25 @@ class StreamingSSG:
             raise ValueError("StreamingSSG: slots must be >= depth + 1")
         self.nslot = nslot
         GB = self.G * batch
-        self.stage = [torch.empty((GB, n, 3), dtype=torch.float32, device=dev) if self.G > 1 else None
-                      for _ in range(nslot)]
-        self.staged = [self.G > 1] * nslot  # the slot's group lives in stage[slot] (else in the caller's batch)
-        self.idx = [torch.empty((GB, self.M1), dtype=torch.int32, device=dev) for _ in range(nslot)]
-        self.cxyz = [torch.empty((GB, self.M1, 3), dtype=torch.float32, device=dev) for _ in range(nslot)]
-        self.fz = [torch.empty(GB, dtype=torch.int32, device=dev) for _ in range(nslot)]
-        # level-0 ball-query indices computed on the side streams (bq="side"; with "bin" the MLP kernel
-        # answers them from the side streams' grids)
-        self.side_q = [bq == "side" for br in lvl0["branches"]]
-        self.gidx = [[torch.empty((GB, self.M1, br["ns"]), dtype=torch.int32, device=dev) if sq else None
-                      for br, sq in zip(lvl0["branches"], self.side_q)]
-                     for _ in range(nslot)] if any(self.side_q) else None
-        self.grid = [[ball_query_grid_buffer(GB, n, dev) for br in lvl0["branches"]]
-                     for _ in range(nslot)] if bq == "bin" else None
-        lvl1 = backbone.levels[1] if len(backbone.levels) > 1 else None
-        self.l2 = bool(l2_side) and lvl1 is not None and not lvl1.get("group_all")
-        if self.l2:
-            self.M2 = max(1, n // lvl1["div"])
-            self.idx2 = [torch.empty((GB, self.M2), dtype=torch.int32, device=dev) for _ in range(nslot)]
-            self.cxyz2 = [torch.empty((GB, self.M2, 3), dtype=torch.float32, device=dev) for _ in range(nslot)]
-            self.fz2 = [torch.empty(GB, dtype=torch.int32, device=dev) for _ in range(nslot)]
-            self.gidx2 = [[torch.empty((GB, self.M2, br["ns"]), dtype=torch.int32, device=dev)
-                           for br in lvl1["branches"]] for _ in range(nslot)]
+        # the levels whose FPS the side streams run: (level, centroids per frame, ball queries there,
+        # their binning there).  Level 0's queries run there with bq="side"; with "bin" the MLP kernel
+        # answers them on the main stream from the side streams' grids
+        lv = backbone.levels
+        self.side = [(lv[0], max(1, n // lv[0]["div"]), bq == "side", bq == "bin")]
+        if l2_side and len(lv) > 1 and not lv[1].get("group_all"):
+            self.side.append((lv[1], max(1, n // lv[1]["div"]), True, False))
+        # the slots' buffers, allocated kind by kind over all slots (not slot by slot): the order, and so the
+        # placement in device memory, under which the executor's recorded speeds were measured
+        new = lambda dtype, *shape: [torch.empty(shape, dtype=dtype, device=dev) for _ in range(nslot)]
+        stage = new(torch.float32, GB, n, 3) if self.G > 1 else [None] * nslot
+        levels = [[] for _ in range(nslot)]
+        for lvl, M, idx, grid in self.side:
+            fps = zip(new(torch.int32, GB, M), new(torch.float32, GB, M, 3), new(torch.int32, GB))
+            for sl, f in zip(levels, fps):
+                sl.append({"fps": f,
+                           "bq": [torch.empty((GB, M, br["ns"]), dtype=torch.int32, device=dev)
+                                  for br in lvl["branches"]] if idx else None,
+                           "grid": [ball_query_grid_buffer(GB, n, dev) for _ in lvl["branches"]] if grid else None})
         # setup-time workspace sizing of the side handles (FPS + ball queries), so no stage's
         # first call grows a workspace (lidar_reserve; growth retires the old block, no device sync)
         if reserve:
@@ -1031,108 +1040,92 @@ class StreamingSSG:
             need = max(lib.lidar_fps_workspace_bytes(GB, n), lib.lidar_ball_query_grid_bytes(GB, n))
             for sl in range(1, depth + 1):
                 nat.call("lidar_reserve", nat.handle(dev.index, sl), need)
-        self.fps_done = [torch.cuda.Event() for _ in range(nslot)]
-        self.slot_free = [torch.cuda.Event() for _ in range(nslot)]
-        for e in self.slot_free:
-            e.record(torch.cuda.current_stream(dev))
+        main = torch.cuda.current_stream(dev)
+        self.slots = [_Slot(st, pre, main) for st, pre in zip(stage, levels)]
 
-    def _stage(self, slot, fs, main):
+    def _stage(self, s, fs, main):
         """The slot's staging buffer (allocated on first use when G = 1) — from the pool of the side stream
         that writes it: a block the caching allocator took from the main stream's pool could be one a
         main-stream pass still queued on the device has just freed, and the side stream does not wait
         for the main stream.  Main-stream passes read it too (record_stream: its block outlives them)."""
-        if self.stage[slot] is None:
+        if s.stage is None:
             with torch.cuda.stream(fs):
-                st = torch.empty((self.G * self.B, self.N, 3), dtype=torch.float32, device=self.bb.device)
-            st.record_stream(main)
-            self.stage[slot] = st
-        return self.stage[slot]
+                s.stage = torch.empty((self.G * self.B, self.N, 3), dtype=torch.float32, device=self.bb.device)
+            s.stage.record_stream(main)
+        return s.stage
+
+    def _copy_in(self, x, xs, fs):
+        """The group's batches into its staging rows x, on the side stream fs (the current stream): a
+        device batch by its own copy, a run of host batches by one."""
+        B, j = self.B, 0
+        grp = None
+        while j < len(xs):
+            if isinstance(xs[j], _HostBatch):
+                # a run of host batches (consecutive rows of one pinned group buffer): one DMA copy
+                e = j
+                while e + 1 < len(xs) and isinstance(xs[e + 1], _HostBatch):
+                    e += 1
+                grp = xs[j].grp
+                x[j * B:(e + 1) * B].copy_(grp.pinned[j * B:(e + 1) * B], non_blocking=True)
+                j = e + 1
+            else:
+                x[j * B:(j + 1) * B].copy_(xs[j], non_blocking=True)
+                j += 1
+        if grp is not None:  # the group buffer may be refilled once its copies have completed
+            grp.copied.record(fs)
 
     def _fps(self, k, xs, ready, main=None):
-        """SA1 FPS + level-0 ball queries of group k (the batches in xs, readable after the
-        events in `ready`) on a side stream; `main` the stream the group's MFMA levels will run on."""
+        """SA1 FPS + level-0 ball queries (and what else self.side lists) of group k (the batches in xs,
+        readable after the events in `ready`) on a side stream; `main` the stream the group's MFMA levels
+        will run on."""
         slot = k % self.nslot
+        s = self.slots[slot]
         fs = self.fps_streams[k % self.depth]
         hs = 1 + k % self.depth  # the side stream's own library handle
-        fs.wait_event(self.slot_free[slot])
+        fs.wait_event(s.slot_free)
         for ev in ready:
             fs.wait_event(ev)
         g = len(xs) * self.B
         t = self.bb.timers
-        host = any(isinstance(xj, _HostBatch) for xj in xs)
-        self.staged[slot] = self.G > 1 or host
-        if self.staged[slot]:
-            self._stage(slot, fs, main if main is not None else torch.cuda.current_stream(self.bb.device))
+        s.staged = self.G > 1 or any(isinstance(xj, _HostBatch) for xj in xs)
+        if s.staged:
+            self._stage(s, fs, main if main is not None else torch.cuda.current_stream(self.bb.device))
         with torch.cuda.stream(fs):
-            if self.staged[slot]:
-                x = self.stage[slot][:g]
-                B, j = self.B, 0
-                grp = None
-                while j < len(xs):
-                    if isinstance(xs[j], _HostBatch):
-                        # a run of host batches (consecutive rows of one pinned group buffer): one DMA copy
-                        e = j
-                        while e + 1 < len(xs) and isinstance(xs[e + 1], _HostBatch):
-                            e += 1
-                        grp = xs[j].grp
-                        x[j * B:(e + 1) * B].copy_(grp.pinned[j * B:(e + 1) * B], non_blocking=True)
-                        j = e + 1
-                    else:
-                        x[j * B:(j + 1) * B].copy_(xs[j], non_blocking=True)
-                        j += 1
-                if grp is not None:  # the group buffer may be refilled once its copies have completed
-                    grp.copied.record(fs)
+            if s.staged:
+                x = s.stage[:g]
+                self._copy_in(x, xs, fs)
             else:
                 x = xs[0]
             for xj in xs:  # read on this stream: keep the caller's buffers alive until then
                 if not isinstance(xj, _HostBatch):
                     xj.record_stream(fs)
-            _call(t, "sa1_fps", g, farthest_point_sample, x, self.M1, return_xyz=True, first_zero=self.fz[slot][:g],
-                  slot=hs, out_idx=self.idx[slot][:g], out_xyz=self.cxyz[slot][:g], threads=self.fps_threads)
-            lvl0 = self.bb.levels[0]
-            for bi_, br in enumerate(lvl0["branches"]):
-                tag = "sa1" + (f"_b{bi_}" if len(lvl0["branches"]) > 1 else "")
-                if self.bq == "side":
-                    _call(t, f"{tag}_ball_query", g, ball_query, br["r"], br["ns"], x, self.cxyz[slot][:g],
-                          out=self.gidx[slot][bi_][:g], slot=hs)
-                elif self.bq == "bin":  # depends only on the points: the queries run on the main stream
-                    _call(t, f"{tag}_bq_bin", g, ball_query_bin, br["r"], br["ns"], x, self.grid[slot][bi_], slot=hs)
-            if self.l2:
-                c1 = self.cxyz[slot][:g]
-                _call(t, "sa2_fps", g, farthest_point_sample, c1, self.M2, return_xyz=True,
-                      first_zero=self.fz2[slot][:g], prefix_ok=self.fz[slot][:g], slot=hs,
-                      out_idx=self.idx2[slot][:g], out_xyz=self.cxyz2[slot][:g])
-                lvl1 = self.bb.levels[1]
-                for bi_, br in enumerate(lvl1["branches"]):
-                    tag = "sa2" + (f"_b{bi_}" if len(lvl1["branches"]) > 1 else "")
-                    _call(t, f"{tag}_ball_query", g, ball_query, br["r"], br["ns"], c1, self.cxyz2[slot][:g],
-                          out=self.gidx2[slot][bi_][:g], slot=hs)
-
-            self.fps_done[slot].record(fs)
+            src, pfz = x, None
+            for li, ((lvl, M, _, _), lv) in enumerate(zip(self.side, s.pre(g).values())):
+                idx, c, fz = lv["fps"]
+                # (level 1's FPS is nested: the prefix shortcut over SA1's centroids)
+                _call(t, f"sa{li + 1}_fps", g, farthest_point_sample, src, M, return_xyz=True, first_zero=fz,
+                      prefix_ok=pfz, slot=hs, out_idx=idx, out_xyz=c, threads=self.fps_threads if li == 0 else 0)
+                for bi_, br in enumerate(lvl["branches"]):
+                    tag = _tag(li, lvl, bi_)
+                    if lv["bq"] is not None:
+                        _call(t, f"{tag}_ball_query", g, ball_query, br["r"], br["ns"], src, c, out=lv["bq"][bi_],
+                              slot=hs)
+                    elif lv["grid"] is not None:  # depends only on the points: the queries run on the main stream
+                        _call(t, f"{tag}_bq_bin", g, ball_query_bin, br["r"], br["ns"], src, lv["grid"][bi_], slot=hs)
+                src, pfz = c, fz
+            s.fps_done.record(fs)
         return slot
 
     def _rest(self, slot, xs, main):
         """The MFMA levels of a group: one pass over its staged frames (every operator is per
         frame, so the per-batch outputs are views of the group's), split back per batch."""
-        main.wait_event(self.fps_done[slot])
+        s = self.slots[slot]
+        main.wait_event(s.fps_done)
         B, g = self.B, len(xs) * self.B
-        x = self.stage[slot][:g] if self.staged[slot] else xs[0]
-        lvl0 = [self.idx[slot][:g], self.cxyz[slot][:g], self.fz[slot][:g],
-                [gi[:g] if gi is not None else None for gi in self.gidx[slot]] if self.gidx is not None else None]
-        pre2 = None
-        if self.l2:
-            pre2 = {"fps": (self.idx2[slot][:g], self.cxyz2[slot][:g], self.fz2[slot][:g]),
-                    "bq": [gi[:g] for gi in self.gidx2[slot]]}
-
-        if self.keep:  # the slot's buffers are reused by a later group
-            lvl0 = [a.clone() for a in lvl0[:3]] + [[gi.clone() if gi is not None else None for gi in lvl0[3]]
-                                                    if lvl0[3] is not None else None]
-            if pre2 is not None:
-                pre2 = {"fps": tuple(a.clone() for a in pre2["fps"]), "bq": [gi.clone() for gi in pre2["bq"]]}
-        out, levels = self.bb.forward_from_sa1_fps(x, *lvl0, keep_levels=self.keep,
-                                                   grids1=self.grid[slot] if self.grid is not None else None,
-                                                   pre2=pre2)
-        self.slot_free[slot].record(main)
+        x = s.stage[:g] if s.staged else xs[0]
+        # keep_levels: the outputs keep copies (the slot's buffers are reused by a later group)
+        out, levels = self.bb.forward(x, self.keep, pre=s.pre(g, clone=self.keep))
+        s.slot_free.record(main)
         outs = list(out.split(B))
         if not self.keep:
             return outs
@@ -1195,7 +1188,10 @@ class _Feed:
 
     def push_host(self, frames, threads=4):
         """frames: one batch of host frames, a (B, N, 3) array or B arrays of shape (N, 3), of any real
-        dtype (converted to float32 as numpy's astype does).  They are copied into the group's pinned
+        dtype: boolean, integer or floating (converted to float32 as numpy's astype does).  Shape and
+        dtype are checked before the call does anything else: a rejected batch raises ValueError and
+        leaves the feed exactly as it was (no pending group retired, no pinned buffer claimed, nothing
+        buffered).  The frames are copied into the group's pinned
         buffer (G batches of rows) by `threads` host threads (frames split between them; numpy releases
         the GIL in the copy), and the group's side stream copies the buffer to the device ahead of its FPS
         in one DMA copy (a copy per batch, queued behind the side stream's kernels, held the calling
@@ -1205,17 +1201,19 @@ class _Feed:
         in-flight group's main-stream pass (push() issues it when the new group completes), so the main
         stream works while the host fills.  Returns the outputs of the batches that call completed, in
         input order; every output equals forward() of the same frames on the device."""
-        import numpy as _np
         p = self.p
         B, N = p.B, p.N
-        if isinstance(frames, _np.ndarray):
+        if isinstance(frames, np.ndarray):
             if frames.shape != (B, N, 3):
                 raise ValueError(f"push_host: frames must be ({B}, {N}, 3), got {frames.shape}")
             parts = list(frames)
         else:
-            parts = [_np.asarray(f) for f in frames]
+            parts = [np.asarray(f) for f in frames]
             if len(parts) != B or any(f.shape != (N, 3) for f in parts):
                 raise ValueError(f"push_host: {B} frames of shape ({N}, 3) expected")
+        if any(f.dtype.kind not in "biuf" for f in parts):
+            raise ValueError(f"push_host: frames must be boolean, integer or floating, got "
+                             f"{sorted({str(f.dtype) for f in parts})}")
         out = []
         if not self.buf and len(self.pending) >= p.depth:
             # the batch opens a group whose completion would issue the oldest group's main-stream pass:
@@ -1238,7 +1236,7 @@ class _Feed:
 
         def fill(lo):
             for j in range(lo, min(B, lo + step)):
-                _np.copyto(dst[j], parts[j], casting="unsafe")
+                np.copyto(dst[j], parts[j], casting="unsafe")
 
         for f in [self._pool.submit(fill, lo) for lo in range(0, B, step)]:
             f.result()

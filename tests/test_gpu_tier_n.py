@@ -1052,3 +1052,68 @@ def test_streaming_generic_shapes_matches_forward(cuda, bq, l2):
     assert len(got) == len(xs)
     for a, b in zip(got, want):
         assert torch.equal(a, b)
+
+
+def _physical_rows(w, b, cfeat, kin=None, xyz_rows=True):
+    """(W, b) padded as the GEMMs read them: layer 1 (kin None) with canonical rows [x, y, z, f...] as
+    [f..., x, y, z, 0-pad] (k to 16; xyz_rows=False: those three rows zero), a later layer's rows
+    zero-padded to kin; columns and bias zero-padded to a multiple of 128."""
+    c = w.shape[1]
+    cp = -(-c // 128) * 128
+    if kin is None:
+        w = np.concatenate([w[3:], w[:3] if xyz_rows else np.zeros_like(w[:3])])
+        kin = -(-(cfeat + 3) // 16) * 16
+    return np.pad(w, ((0, kin - w.shape[0]), (0, cp - c))), np.pad(b, (0, cp - c))
+
+
+@pytest.mark.parametrize("cfg_name,dtype", [("msg", "bf16"), ("ssg", "f32")])
+def test_backbone_weight_layouts(cuda, cfg_name, dtype):
+    """The padded weights the backbone's constructor builds, against the layout rule applied to bb.weights:
+    the group_all entry's three layers and, in the bf16 spec, every feature-level branch's W1_f (xyz rows zero)."""
+    bb = pn.PointNet2Backbone(pn.CONFIGS[cfg_name], device=cuda, seed=11, dtype=dtype)
+    ga = bb.levels[-1]
+    assert ga.get("group_all") and len(ga["w"]) == len(ga["b"]) == 3
+    kin = None
+    for j, (w, b) in enumerate(bb.weights[-1][0]):
+        ww, wb = _physical_rows(w, b, ga["cfeat"], kin)
+        assert np.array_equal(ga["w"][j].cpu().numpy(), ww), j
+        assert np.array_equal(ga["b"][j].cpu().numpy(), wb), j
+        kin = ww.shape[1]
+    assert ga["w"][0].shape[0] == ga["k"]
+    if dtype == "bf16":
+        lvl = bb.levels[1]
+        assert len(lvl["branches"]) == 3
+        for br, layers in zip(lvl["branches"], bb.weights[1]):
+            ww, wb = _physical_rows(*layers[0], lvl["cfeat"], xyz_rows=False)
+            got = br["pre_x1"]["w1f"].cpu().numpy()
+            assert np.array_equal(got, ww) and got.shape[0] == lvl["k"]
+            assert not got[lvl["cfeat"]:].any()  # the xyz rows (and the padding) are zero
+            assert np.array_equal(br["pre_x1"]["b1"].cpu().numpy(), wb)
+
+
+def test_streaming_host_feed_rejected_batch_drops_nothing(cuda):
+    """push_host validates the whole batch (shape and dtype) before its first side effect: a batch of a dtype
+    that is not boolean, integer or floating, pushed when `depth` groups are pending and no batch is buffered
+    (where the oldest group's main-stream pass is issued early), raises and leaves the feed as it was — every
+    valid batch before and after it still comes out, in order, equal to forward()."""
+    B, N, depth, G = 2, 4096, 2, 2
+    bb = pn.PointNet2Backbone(pn.SSG, device=cuda, seed=12)
+    hx = [unit_frames(B, N, 120 + s) for s in range(depth * G + 5)]
+    want = [bb.forward(torch.from_numpy(h).to(cuda))[0] for h in hx]
+    feed = pn.StreamingSSG(bb, B, N, depth=depth, fps_group=G, ramp=False, bq="bin", l2_side=True).feed()
+    outs = []
+    for h in hx[:depth * G]:
+        outs += feed.push_host(h)
+    assert len(feed.pending) == depth and not feed.buf
+    pending, grp, ri = list(feed.pending), feed._grp, feed._ri
+    with pytest.raises(ValueError, match="push_host"):
+        feed.push_host(np.full((B, N, 3), "x", dtype=object))
+    assert feed.pending == pending and not feed.buf and feed._grp is grp and feed._ri == ri
+    for h in hx[depth * G:]:
+        outs += feed.push_host(h)
+    outs += feed.flush()
+    torch.cuda.synchronize()
+    feed.close()
+    assert len(outs) == len(hx)
+    for i, (a, b) in enumerate(zip(outs, want)):
+        assert torch.equal(a, b), i

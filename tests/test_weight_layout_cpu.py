@@ -1,0 +1,64 @@
+"""The one weight layout of pointnet2 (layer1_weights, generic_branch_weights), against arrays built here
+from the rule their docstrings state: canonical rows [x, y, z, f...] become [f..., x, y, z, 0-pad] with k
+padded to 16, columns (and the next layer's rows) zero-padded to a multiple of 128.  No GPU, no library."""
+import numpy as np
+import pytest
+
+from lidar_ai_recommendation_software_amd import pointnet2 as pn
+
+WIDTHS = [32, 96, 200]  # a cout below, off and above the 128-column tile
+CP = {32: 128, 96: 128, 200: 256}
+KP = {0: 16, 5: 16, 13: 16, 320: 336}  # cfeat + 3 = 3, 8, 16 (on the grid), 323
+same = lambda a: a  # to_dev: the arrays stay on the host
+
+
+def _layers(cfeat, seed):
+    rng = np.random.default_rng(seed)
+    out, cin = [], 3 + cfeat
+    for c in WIDTHS:
+        out.append((rng.standard_normal((cin, c)).astype(np.float32), rng.standard_normal(c).astype(np.float32)))
+        cin = c
+    return out
+
+
+def _want_layer1(w, cfeat):
+    """Feature rows first, then the three xyz rows, zeros to kp; columns zero past c."""
+    c = w.shape[1]
+    return np.pad(np.concatenate([w[3:], w[:3]]), ((0, KP[cfeat] - cfeat - 3), (0, CP[c] - c)))
+
+
+def _check_layer1_weights(cfeat, c1):
+    rng = np.random.default_rng(100 * cfeat + c1)
+    w = rng.standard_normal((3 + cfeat, c1)).astype(np.float32)
+    b = rng.standard_normal(c1).astype(np.float32)
+    got = pn.layer1_weights((w, b), cfeat, same)
+    assert sorted(got) == ["b1", "w1", "wq", "zero"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["w1"].shape == (KP[cfeat], CP[c1])
+    assert np.array_equal(got["w1"], _want_layer1(w, cfeat))
+    assert np.array_equal(got["wq"], np.pad(w[:3], ((0, 13), (0, CP[c1] - c1))))  # the xyz rows over 16
+    assert np.array_equal(got["b1"], np.pad(b, (0, CP[c1] - c1)))
+    assert np.array_equal(got["zero"], np.zeros(CP[c1], np.float32))
+
+
+@pytest.mark.parametrize("cfeat", sorted(KP))
+def test_weight_layout(cfeat):
+    for c1 in WIDTHS:
+        _check_layer1_weights(cfeat, c1)
+    layers = _layers(cfeat, cfeat)
+    got = pn.generic_branch_weights(layers, cfeat, same, arith="f32")
+    assert got["k"] == KP[cfeat] and got["c3"] == WIDTHS[-1] and got["arith"] == "f32"
+    assert len(got["layers"]) == len(WIDTHS)
+    kin = KP[cfeat]
+    for j, ((w, b), lay) in enumerate(zip(layers, got["layers"])):
+        c = w.shape[1]
+        assert sorted(lay) == ["b", "cout", "w"]  # fp32: plain weights, no packed image
+        assert lay["cout"] == CP[c] and lay["w"].shape == (kin, CP[c]) and lay["w"].dtype == np.float32
+        # layer j + 1's rows are padded to layer j's cp
+        want = _want_layer1(w, cfeat) if j == 0 else np.pad(w, ((0, kin - w.shape[0]), (0, CP[c] - c)))
+        assert np.array_equal(lay["w"], want), j
+        assert np.array_equal(lay["b"], np.pad(b, (0, CP[c] - c))), j
+        kin = CP[c]
+    # the two functions agree on layer 1
+    pre = pn.layer1_weights(layers[0], cfeat, same)
+    assert np.array_equal(pre["w1"], got["layers"][0]["w"]) and np.array_equal(pre["b1"], got["layers"][0]["b"])
