@@ -72,8 +72,8 @@ uint64_t lidar_fps_workspace_bytes(int64_t batch, int64_t n);
 
 /* farthest-point sampling: idx (batch, npoint) int32; optionally new_xyz (batch, npoint, 3)
  * = xyz[idx] (pass NULL to skip).  Start index 0, fp32 no-FMA distances, lowest index on
- * ties.  Optional first_zero (batch) receives the first step whose winning distance was 0
- * (npoint if none).  Optional prefix_ok (batch): when xyz are the first points of a parent
+ * ties.  Optional first_zero (batch) receives the first step whose winning distance was 0 or
+ * not finite (npoint if none).  Optional prefix_ok (batch): when xyz are the first points of a parent
  * FPS ordering, pass the parent's first_zero — frames with npoint <= prefix_ok[b] get the
  * exact identity result without running (nested SA levels).  Replaces:
  * downsample_point_cloud's random subset (utils/data_processing.py:231-249) where a
@@ -119,7 +119,8 @@ int lidar_ball_query_binned_f32(lidar_handle *h, const float *xyz, const void *g
  * If pool_rows > 0: y is (rows / pool_rows, cout) = max over each run of pool_rows rows
  * (group_all's max-pool, fused); y must then be zeroed by the caller first.
  * k a multiple of 16, cout a multiple of 128, rows a multiple of 128
- * (pool_rows a multiple of 128 when used). */
+ * (pool_rows a multiple of 128 when used).  ReLU and max-pool propagate NaN (INTEGRATION.md
+ * "Non-finite input"; tests/test_gpu_nonfinite.py). */
 int lidar_dense_relu_f32(lidar_handle *h, const float *x, int64_t rows, int32_t k,
                          const float *w, const float *bias, int32_t cout, int32_t pool_rows,
                          float *y, void *stream);
@@ -141,8 +142,8 @@ int lidar_dense_x3_pack_f32(lidar_handle *h, const float *w, int32_t k, int32_t 
 int lidar_dense_x1_pack_f32(lidar_handle *h, const float *w, int32_t k, int32_t cout, void *packed, void *stream);
 
 /* y = x W + b on that image (csrc/dense_x3s.hip): A = fp32 rows (rows, k) of row stride lda
- * (k % 4 == 0; elements k..lda-1 are read and must be finite), each wave scales and splits the
- * fragments it reads.  mode 0: y [ReLU] as fp32 rows (rows, ldo); mode 2: ReLU and max over runs
+ * (k % 4 == 0, lda % 4 == 0; elements k..lda-1 are never read and may hold anything, as may columns
+ * cout..ldo-1 of out, which are never written), each wave scales and splits the fragments it reads.  mode 0: y [ReLU] as fp32 rows (rows, ldo); mode 2: ReLU and max over runs
  * of pool_rows rows into fp32 (rows/pool_rows, ldo), out zeroed by the caller.  rows % 128 == 0,
  * cout % 128 == 0; o_plane is unused (0).  Mode flag 4 (mode 0 only, lidar_dense_x1_pack_f32's
  * image): one bf16 product per MFMA, bf16(x) bf16(w) in fp32 — the bf16 spec. */
@@ -151,14 +152,17 @@ int lidar_dense_x3f_f32(lidar_handle *h, const float *a, int32_t lda, int64_t ro
                         int64_t o_plane, int64_t ldo, void *stream);
 
 /* group_all's h3 chain (csrc/dense_x3s.hip): the same GEMM with the activations split ONCE, by the
- * producing layer.  A: fp32 rows (a_exp NULL; k % 4 == 0, lda % 4 == 0, elements k..lda-1 read and
- * finite) or h3 planes (a_exp (rows,) int32: |x| < 2^e per row; the fp16 hi plane (rows, lda) at a, the
+ * producing layer.  A: fp32 rows (a_exp NULL; k % 4 == 0, lda % 4 == 0, elements k..lda-1 never
+ * read) or h3 planes (a_exp (rows,) int32: |x| < 2^e per row; the fp16 hi plane (rows, lda) at a, the
  * lo plane at a + rows*lda halves, hi + lo = x 2^(14 - e) up to 2^-22; lda = k rounded up to 32, zeros
  * past k) — what mode 1 writes.  mode 0: fp32 rows (rows, ldo) [+ ReLU]; 1: h3 planes of y [+ ReLU]
  * (hi at out, lo at out + rows*ldo halves, ldo == cout) and out_exp (rows,): an exponent bound shared
  * by every column tile, 2^e_in w_colsum + b_max (w_colsum >= max_c sum_k |W_kc|, b_max >= max |b|,
  * the caller's, rounded up); 2: ReLU and max over runs of pool_rows rows (fp32, out zeroed by the
- * caller).  rows % 128 == 0, cout % 128 == 0; packed: lidar_dense_x3_pack_f32's image. */
+ * caller).  rows % 128 == 0, cout % 128 == 0; packed: lidar_dense_x3_pack_f32's image.
+ * Non-finite operands, both entry points and every mode: INTEGRATION.md "Non-finite input" (a row or
+ * pool group an inf / NaN reaches is non-finite wherever fp32 would be, ReLU and max-pool included; the
+ * other rows and groups are bit-identical; tests/test_gpu_nonfinite.py). */
 int lidar_dense_h3p_f32(lidar_handle *h, const void *a, int32_t lda, int64_t rows, int32_t k, const int32_t *a_exp,
                         const void *packed, const float *bias, int32_t cout, int32_t mode, int32_t relu_on,
                         int32_t pool_rows, void *out, int32_t *out_exp, int64_t ldo, float w_colsum, float b_max,
@@ -191,7 +195,10 @@ int lidar_sa_group_mlp_x1_f32(lidar_handle *h, int32_t layer1_mode, const float 
  * centre W1_xyz (lidar_dense_f32 / lidar_dense_x3f_f32, relu off); a grouped row's layer 1 is
  * relu(p[k] - q[c]).
  * packed: the lidar_mlp_pack16_f32 image of lidar_mlp_packed_size16 floats (w1 is read only
- * for an xyz level: its 3 xyz rows).  Same outputs up to fp32 re-association. */
+ * for an xyz level: its 3 xyz rows).  Same outputs up to fp32 re-association.
+ * Non-finite points, centres or features (this kernel and the x3 / x1 / bq variants below): a centre
+ * that one reaches is non-finite wherever the fp32 pipeline's relu / max_pool2d would be, every other
+ * centre is bit-identical (INTEGRATION.md "Non-finite input"; tests/test_gpu_nonfinite.py). */
 int64_t lidar_mlp_packed_size16(int32_t xyz_level, int32_t c1, int32_t c2, int32_t c3);
 int lidar_mlp_pack16_f32(int32_t xyz_level, int32_t c1, int32_t c2, int32_t c3, const float *w1_host,
                          const float *b1_host, const float *w2_host, const float *b2_host,

@@ -201,6 +201,15 @@ __device__ __forceinline__ float wave_min_f(float v)
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// The MLP kernels' max and ReLU: NaN-propagating, as the fp32 pipeline they replace (relu and
+// max_pool2d) and numpy's maximum — `v > 0 ? v : 0` and fmaxf drop a NaN, and an integer max of the
+// bits with 0 drops one whose sign bit is set (inf - inf on this hardware).  v_maximum3_f32: one
+// VALU op, no canonicalising v_max on MFMA results.  On finite input relu_nan equals
+// `v > 0 ? v : 0` bit for bit (-0 gives +0).  INTEGRATION.md "Non-finite input";
+// tests/test_gpu_nonfinite.py.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
 }  // namespace lidar
 
 // ----------------------------------------------------------------- DPP wave reductions

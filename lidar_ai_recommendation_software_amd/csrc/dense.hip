@@ -19,7 +19,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c)
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
+using lidar::max_nan;
+using lidar::relu_nan;
 
 // ------------------------------------------------------------------ dense GEMM
 constexpr int BM = 128, BN = 128, BK = 16;
@@ -80,18 +81,19 @@ __global__ __launch_bounds__(256) void dense_relu_kernel(const float *__restrict
                 for (int r = 0; r < 16; ++r) {
                     const int64_t row = row0 + wm * 64 + i * 32 + rho(r) + 4 * h;
                     const float v = acc[i][j][r] + bb;
-                    y[row * cout + c] = act ? relu(v) : v;
+                    y[row * cout + c] = act ? relu_nan(v) : v;
                 }
         } else {
             float v = 0.0f;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) v = fmaxf(v, relu(acc[i][j][r] + bb));
-            v = fmaxf(v, __shfl_xor(v, 32, 64));
+                for (int r = 0; r < 16; ++r) v = max_nan(v, relu_nan(acc[i][j][r] + bb));
+            v = max_nan(v, __shfl_xor(v, 32, 64));
             if (h == 0) {
                 // non-negative floats order as their bit patterns: an unsigned max is exact
-                // and order-independent (deterministic)
+                // and order-independent (deterministic); a NaN's bits (either sign) are above
+                // every finite value's, so a NaN stays
                 unsigned *dst = reinterpret_cast<unsigned *>(y + (row0 / pool_rows) * cout + c);
                 atomicMax(dst, __float_as_uint(v));
             }

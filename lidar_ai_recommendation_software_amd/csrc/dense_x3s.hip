@@ -67,7 +67,7 @@ __device__ __forceinline__ void lds_dma16(const void *g, void *l)
                                      (__attribute__((address_space(3))) void *)l, 16, 0, 0);
 }
 
-__device__ __forceinline__ float relu_i(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
+using lidar::relu_nan;  // NaN-propagating, either sign (common.hpp; tests/test_gpu_nonfinite.py)
 
 // NaN-propagating max over the 32 lanes of each half-wave, in every lane of it: four DPP steps
 // within each 16-lane row, then v_permlane16_swap's xor-16 partner
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const float y = acc[j][4 * g + t] + b4[t];
-                    v[t] = (relu_on ? relu_i(y) : y) * so;
+                    v[t] = (relu_on ? relu_nan(y) : y) * so;
                 }
                 uint32_t hi[2], lo[2];
                 lidar_h3::split2(v[0], v[1], hi[0], lo[0]);
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const float y = acc[j][4 * g + t] + b4[t];
-                    v[t] = relu_on ? relu_i(y) : y;
+                    v[t] = relu_on ? relu_nan(y) : y;
                 }
                 *reinterpret_cast<f32x4 *>(out + row * ldo + c) = v;
             }
@@ -340,7 +340,8 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
         unsigned *orow = reinterpret_cast<unsigned *>(out + (row0 / pool_rows) * ldo);
         // the max over the wave's 32 rows per channel, over the 32 lanes of each h; then an atomic
         // max across waves and workgroups.  relu(max + b) == max relu(x + b) (x -> relu(x + b) is
-        // monotone); non-negative floats order as their bits: exact, order-free
+        // monotone); non-negative floats order as their bits: exact, order-free.  A NaN survives
+        // the lane maxima and the ReLU, and its bits (either sign) are above every finite value's
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float mine = 0.0f;  // lane col < 16 of each half-wave takes register col's max
@@ -351,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
             }
             if (col < 16) {  // one 32-lane atomic per tile (not one per register)
                 const int c = cbase + 32 * j + 8 * (col >> 2) + 4 * h + (col & 3);
-                atomicMax(orow + c, __float_as_uint(relu_i(mine + bias[c])));
+                atomicMax(orow + c, __float_as_uint(relu_nan(mine + bias[c])));
             }
         }
     }
@@ -362,7 +363,8 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
 int lidar_dense_x3_packed_image(int32_t k, int32_t cout, int64_t *bytes);  // x3_pack.hip
 
 // the GEMM with A as fp32 rows (rows, lda) (split inside the tile loop; elements k..lda-1 are
-// read and must be finite — weights there are zero).  mode 0: fp32 rows out (rows, ldo);
+// never read: a stage's chunks at or past k re-read its first chunk, whose weights there are zero —
+// tests/test_gpu_nonfinite.py::test_dense_padding_beside_the_operands).  mode 0: fp32 rows out (rows, ldo);
 // mode 2: fp32 max over runs of pool_rows rows (ReLU; out zeroed by the caller).  mode | 4: the
 // bf16 spec (X1) on lidar_dense_x1_pack_f32's image (mode 0 only); otherwise packed =
 // lidar_dense_x3_pack_f32's h3 image.
@@ -409,8 +411,8 @@ LIDAR_EXPORT int lidar_dense_x3f_f32(lidar_handle *h, const float *a, int32_t ld
     return LIDAR_OK;
 }
 
-// The h3 chain of group_all: A as fp32 rows (a_exp NULL; lda % 4 == 0, elements k..lda-1 read and
-// finite) or as h3 planes (a_exp (rows,) int32 the rows' exponents, |x| < 2^e: hi plane (rows, lda)
+// The h3 chain of group_all: A as fp32 rows (a_exp NULL; lda % 4 == 0, elements k..lda-1 never
+// read) or as h3 planes (a_exp (rows,) int32 the rows' exponents, |x| < 2^e: hi plane (rows, lda)
 // fp16 at a, lo plane at a + rows * lda halves; lda = k rounded up to 32, zeros past k — what mode 1
 // writes).  mode 0: fp32 rows (rows, ldo) [+ ReLU]; 1: h3 planes of y [+ ReLU] (hi at out, lo at
 // out + rows * ldo halves, ldo % 8 == 0) and out_exp (rows,) — their exponent, from the bound

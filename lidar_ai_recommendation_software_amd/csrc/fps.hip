@@ -23,9 +23,10 @@
 // coordinates to a per-wave slot, so the frame argmax costs a single barrier per step.
 //
 // Nested FPS (SA2 samples SA1's centroids): FPS over the first m points of an FPS ordering
-// is the identity 0..m-1 while the parent's winning distance stayed > 0 — the parent
-// run records the first step whose winning distance was 0 (`first_zero`), the child run
-// takes it as `prefix_ok` and copies the prefix when m <= prefix_ok.
+// is the identity 0..m-1 while the parent's winning distance stayed > 0 and finite — the parent
+// run records the first step whose winning distance was 0, inf or NaN (`first_zero`), the child run
+// takes it as `prefix_ok` and copies the prefix when m <= prefix_ok (DESIGN.md §3.1;
+// tests/test_gpu_nonfinite.py::test_backbone_nonfinite_frame: a frame with an inf point).
 #include <algorithm>
 #include <atomic>
 
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
     const float *p = xyz + (int64_t)b * n * 3;
 
     // nested FPS shortcut: FPS over the first m points of an FPS ordering returns 0..m-1
-    // as long as the parent's winning distance stayed > 0 — exact.
+    // as long as the parent's winning distance stayed > 0 and finite — exact.
     if (prefix_ok != nullptr && prefix_ok[b] >= npoint) {
         for (int i = tid; i < npoint; i += T) {
             out_idx[(int64_t)b * npoint + i] = i;
@@ -390,7 +391,11 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
 #pragma unroll
         for (int a = 0; a < 3; ++a) bx[q][a] = 0.0f;
         bp[q] = -1;
-        bd[q] = have ? INFINITY : 0.0f;  // empty slot: never active, never the argmax
+        // a bucket's key is a placeholder until its first update: NaN bits, above every lower bound in the
+        // bit-space test below, so step 1 updates every bucket — also one whose lower bound is inf (all its
+        // points have an inf coordinate, or squared distances that overflow), which `lb < inf` left with
+        // the placeholder (inf, index 0) as the frame's argmax.  Empty slot: never active, never the argmax
+        bd[q] = have ? __int_as_float(0x7fc00000) : 0.0f;
         bi[q] = have ? 0u : 0xffffffffu;
     }
 
@@ -405,7 +410,7 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
             o[2] = qz;
         }
     }
-    int zero_at = npoint;  // first step whose winning distance is 0
+    int zero_at = npoint;  // first step whose winning distance is 0 or non-finite
 
     float w_d = 0.0f, w_x = 0.0f, w_y = 0.0f, w_z = 0.0f;  // this wave's current argmax
     uint32_t w_i = 0xffffffffu;
@@ -428,7 +433,9 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
             const float gy = gap(qy, bmin[q][1], bmax[q][1]);
             const float gz = gap(qz, bmin[q][2], bmax[q][2]);
             const float lb = __fadd_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)), __fmul_rn(gz, gz));
-            uint64_t mask = __ballot(lb < bd[q]);
+            // lb and every real bd are >= +0 and never NaN (gap() ends in fmaxf(., 0)): the signed order of
+            // their bits is their float order
+            uint64_t mask = __ballot(__float_as_int(lb) < __float_as_int(bd[q]));
             // the wave argmax is recomputed only when its bucket's key changed
             const int target = q == w_q ? w_lane : -1;
             while (mask) {  // wave-uniform
@@ -521,7 +528,6 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
             if (lane < (T / 64))  // 16 lanes read: 256 B per wave instead of 1 KiB of LDS traffic
                 cand = *reinterpret_cast<const float4 *>(mcrd[cslot][lane]);
             const int ww = __builtin_amdgcn_readfirstlane((int)(key & 15u));
-            const float gdist = __uint_as_float((uint32_t)(key >> 32));
             const uint32_t gidx = (1u << 27) - (((uint32_t)key) >> 4);
             qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.x), ww));
             qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.y), ww));
@@ -535,7 +541,12 @@ __global__ __launch_bounds__(T) void fps_bucket_kernel(const float *__restrict__
                     o[2] = qz;
                 }
             }
-            if (zero_at == npoint && gdist == 0.0f) zero_at = it;
+            // 0, or inf / NaN: a point with a non-finite coordinate, or one whose squared distances
+            // overflow, keeps dist = inf for ever (no d is < inf once d is inf or NaN) and wins every
+            // later step, so the ordering repeats it exactly as it does after a 0.  On the bits, in
+            // scalar registers (the key is wave-uniform): bits - 1 wraps 0 above every finite value
+            const uint32_t gbits = (uint32_t)__builtin_amdgcn_readfirstlane((int)(key >> 32));
+            if (zero_at == npoint && gbits - 1u >= 0x7f7fffffu) zero_at = it;
         }
         cur3 = nxt3;
         nxt3 = nxt3 == 2 ? 0 : nxt3 + 1;

@@ -21,6 +21,10 @@
 // inf one is NaN, so every output an inf or NaN operand reaches is NaN in h3 where fp32 would give
 // +-inf or NaN: non-finite outputs stay non-finite (tests/test_gpu_tier_n.py::test_dense_x3s_nonfinite),
 // only the class (inf vs NaN) may differ.  Finite rows are unaffected (scaling groups are per row / tile).
+// The rule holds through ReLU and max-pool too: inf - inf is a NaN with the sign bit SET on this hardware,
+// so every ReLU and max after an h3 product is NaN-propagating for either sign (lidar::relu_nan /
+// max_nan, common.hpp), never an integer max of the bits with 0 nor fmaxf — a poisoned row, pool group or
+// centre comes out non-finite, not as zeros (tests/test_gpu_nonfinite.py; INTEGRATION.md "Non-finite input").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

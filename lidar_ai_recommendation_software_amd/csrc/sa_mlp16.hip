@@ -29,7 +29,8 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c)
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
+using lidar::max_nan;
+using lidar::relu_nan;
 
 // packed image (floats): [W1: T1*64 (XYZ levels only, see below)] [chunks of layer 2]
 // [chunks of layer 3] [b1 C1] [b2 C2] [b3 C3].  A chunk covers output tiles (2c, 2c+1) of a
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(64 * WPG, 4) void sa16_kernel(const float *__restri
                 f32x4 acc = {};
                 acc = mfma16(w1_s[t * 64 + lane], x, acc);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc[r] = relu(acc[r] + bias_s[16 * t + 4 * q + r]);
+                for (int r = 0; r < 4; ++r) acc[r] = relu_nan(acc[r] + bias_s[16 * t + 4 * q + r]);
                 y1[t] = acc;
             }
         } else {
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(64 * WPG, 4) void sa16_kernel(const float *__restri
             for (int ti = 0; ti < T1; ++ti) {
                 const f32x4 a = pp[4 * ti], c = qq[4 * ti];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) y1[ti][r] = relu(a[r] - c[r]);
+                for (int r = 0; r < 4; ++r) y1[ti][r] = relu_nan(a[r] - c[r]);
             }
         }
 
@@ -167,8 +168,8 @@ __global__ __launch_bounds__(64 * WPG, 4) void sa16_kernel(const float *__restri
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    a0[r] = relu(a0[r] + bias_s[C1 + 16 * (2 * c) + 4 * q + r]);
-                    a1[r] = relu(a1[r] + bias_s[C1 + 16 * (2 * c + 1) + 4 * q + r]);
+                    a0[r] = relu_nan(a0[r] + bias_s[C1 + 16 * (2 * c) + 4 * q + r]);
+                    a1[r] = relu_nan(a1[r] + bias_s[C1 + 16 * (2 * c + 1) + 4 * q + r]);
                 }
                 y2[2 * c < T2 ? 2 * c : 0] = a0;
                 y2[2 * c + 1 < T2 ? 2 * c + 1 : 0] = a1;
@@ -193,12 +194,12 @@ __global__ __launch_bounds__(64 * WPG, 4) void sa16_kernel(const float *__restri
                     const float bias = bias_s[C1 + C2 + 16 * t + col];
                     float v = 0.0f;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v = fmaxf(v, relu(acc[r] + bias));
-                    v = fmaxf(v, __shfl_xor(v, 16, 64));
-                    v = fmaxf(v, __shfl_xor(v, 32, 64));
+                    for (int r = 0; r < 4; ++r) v = max_nan(v, relu_nan(acc[r] + bias));
+                    v = max_nan(v, __shfl_xor(v, 16, 64));
+                    v = max_nan(v, __shfl_xor(v, 32, 64));
                     if (q == 0) {
                         float &m = mx_s[wave][(t < T3 ? 16 * t : 0) + col];
-                        m = fmaxf(m, v);
+                        m = max_nan(m, v);
                     }
                 }
             }

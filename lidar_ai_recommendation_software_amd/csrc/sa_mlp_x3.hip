@@ -45,10 +45,9 @@ __device__ __forceinline__ f32x4 mfma_f(float a, float b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ float relu(float v) { return v > 0.0f ? v : 0.0f; }
-// ReLU on the bits (signed int max with 0): no canonicalising v_max on MFMA results; equal to
-// relu() except that a positive NaN stays NaN
-__device__ __forceinline__ float relu_i(float v) { return __int_as_float(max(__float_as_int(v), 0)); }
+// every ReLU here propagates NaN of either sign (common.hpp): a centre that a non-finite value
+// reaches comes out non-finite, never as zeros (tests/test_gpu_nonfinite.py)
+using lidar::relu_nan;
 // max of three, NaN-propagating (v_maximum3_f32: no canonicalising v_max per operand, which
 // fmaxf's quiet-NaN rule costs on MFMA results)
 __device__ __forceinline__ float maxn(float a, float b, float c)
@@ -264,7 +263,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
                     f32x4 acc = *reinterpret_cast<const f32x4 *>(&bias_s[16 * t + 4 * q]);
                     acc = mfma_f(w1_s[t * 64 + lane], x, acc);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = relu_i(acc[r]);
+                    for (int r = 0; r < 4; ++r) acc[r] = relu_nan(acc[r]);
                     y1[t] = acc;
                 }
             } else if constexpr (L1 == L1_PX) {
@@ -276,7 +275,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
                 for (int t = 0; t < T1; ++t) {
                     f32x4 acc = mfma_f(w1_s[t * 64 + lane], x, pp[4 * t]);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = relu_i(acc[r]);
+                    for (int r = 0; r < 4; ++r) acc[r] = relu_nan(acc[r]);
                     y1[t] = acc;
                 }
             } else {
@@ -290,7 +289,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
                 for (int ti = 0; ti < T1; ++ti) {
                     const f32x4 a = pp[4 * ti], c = qq[4 * ti];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) y1[ti][r] = relu(a[r] - c[r]);
+                    for (int r = 0; r < 4; ++r) y1[ti][r] = relu_nan(a[r] - c[r]);
                 }
             }
             float sc = 1.0f;
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
 #pragma unroll
                 for (int t = 0; t < T1; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) mb = max(mb, __float_as_uint(y1[t][r]));  // ReLU outputs: non-negative bits
+                    for (int r = 0; r < 4; ++r) mb = max(mb, __float_as_uint(y1[t][r]));  // ReLU outputs: non-negative bits, or a NaN (its centre is NaN whatever the scale)
                 e2[rr] = lidar_h3::wave_exp(mb);
                 sc = lidar_h3::scale_of(e2[rr]);
             }
@@ -365,8 +364,8 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
                             a0[rr][r] = fmaf(a0[rr][r], us, b0[r]);
                             a1[rr][r] = fmaf(a1[rr][r], us, b1[r]);
                         }
-                        a0[rr][r] = relu_i(a0[rr][r]);
-                        a1[rr][r] = relu_i(a1[rr][r]);
+                        a0[rr][r] = relu_nan(a0[rr][r]);
+                        a1[rr][r] = relu_nan(a1[rr][r]);
                     }
                     y2[rr][2 * c < T2 ? 2 * c : 0] = a0[rr];
                     y2[rr][2 * c + 1 < T2 ? 2 * c + 1 : 0] = a1[rr];
@@ -385,7 +384,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
 #pragma unroll
                             for (int t = 0; t < T2; ++t)
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) mb = max(mb, __float_as_uint(y2[rr][t][r]));  // ReLU outputs: non-negative bits
+                                for (int r = 0; r < 4; ++r) mb = max(mb, __float_as_uint(y2[rr][t][r]));  // ReLU outputs: non-negative bits, or a NaN (its centre is NaN whatever the scale)
                             e3[rr] = lidar_h3::wave_exp(mb);
 #endif
                             sc = lidar_h3::scale_of(e3[rr]);
@@ -447,7 +446,7 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
 #pragma unroll
         for (int j = 0; j < T3 / 4; ++j) {
             const int c3 = 16 * (4 * j + q) + col;
-            o[c3] = relu(mx[j] + bias_s[C1 + C2 + c3]);
+            o[c3] = relu_nan(mx[j] + bias_s[C1 + C2 + c3]);
         }
     }
 }
@@ -573,8 +572,8 @@ __global__ __launch_bounds__(256, LIDAR_LEAN_W) void sa_x3_lean_kernel(const flo
                         const f32x4 a = pp[4 * (2 * s + h)], c = qq[4 * (2 * s + h)];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            y[s][h][r] = relu(a[r] - c[r]);
-                            mb = max(mb, __float_as_uint(y[s][h][r]));  // ReLU outputs: non-negative bits
+                            y[s][h][r] = relu_nan(a[r] - c[r]);
+                            mb = max(mb, __float_as_uint(y[s][h][r]));  // ReLU outputs: non-negative bits, or a NaN (its centre is NaN whatever the scale)
                         }
                     }
                 e2 = lidar_h3::wave_exp(mb);
@@ -609,8 +608,8 @@ __global__ __launch_bounds__(256, LIDAR_LEAN_W) void sa_x3_lean_kernel(const flo
                 const float us = ldexpf(1.0f, e2 - 14 - tl.s2);  // 2^-(s_a + s_w): one exact fma with the bias
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    a0[r] = relu_i(fmaf(a0[r], us, b0[r]));
-                    a1[r] = relu_i(fmaf(a1[r], us, b1[r]));
+                    a0[r] = relu_nan(fmaf(a0[r], us, b0[r]));
+                    a1[r] = relu_nan(fmaf(a1[r], us, b1[r]));
                 }
                 split_pair(a0, a1, zh[rr][c], zl[rr][c], sc3);  // layer-2 chunk c = layer-3 k-step c
                 if constexpr ((LIDAR_SA_ABL & 2) == 0) __syncthreads();
@@ -664,7 +663,7 @@ __global__ __launch_bounds__(256, LIDAR_LEAN_W) void sa_x3_lean_kernel(const flo
 #pragma unroll
         for (int j = 0; j < T3 / 4; ++j) {
             const int c3 = 16 * (4 * j + q) + col;
-            o[c3] = relu(mx[j] + bias_s[C2 + c3]);
+            o[c3] = relu_nan(mx[j] + bias_s[C2 + c3]);
         }
     }
 }

@@ -141,7 +141,7 @@ def farthest_point_sample(xyz, npoint, return_xyz=False, first_zero=None, prefix
     threads: workgroup size per frame (0 = 1024, 512; frames above 262 144 points always take 512).
     n <= 4 194 304 points per frame.
 
-    first_zero: optional (B,) int32 output — first step whose winning distance was 0.
+    first_zero: optional (B,) int32 output — first step whose winning distance was 0 or not finite.
     prefix_ok: optional (B,) int32 — the parent run's first_zero when xyz is the parent's
     FPS-ordered sample set (nested SA levels): the exact identity result is copied."""
     _dev_check(xyz, first_zero, prefix_ok)
