@@ -255,6 +255,32 @@ int lidar_sa_group_rows_f32(lidar_handle *h, const float *feat, int64_t ldf, int
 int lidar_group_max_f32(lidar_handle *h, const float *in, int64_t ldi, int64_t groups, int32_t nsample, int32_t c,
                         float *out, int64_t ldo, int64_t out_offset, void *stream);
 
+/* PointNet++ feature propagation (csrc/feature_prop.hip; DESIGN.md §3 "Feature propagation"): the
+ * decoder's operators, pointnet2's three_nn / three_interpolate of PointnetFPModule (no reference
+ * counterpart: SURVEY §0).  All fp32, one rounding per operation, reproducible bit for bit in numpy.
+ *
+ * lidar_three_nn_f32: unknown (batch, n, 3), known (batch, m, 3), n >= 1, 1 <= m < 2^31.  Per unknown
+ * point the three smallest d(j) = (dx*dx + dy*dy) + dz*dz over its frame's known points in
+ * lexicographic (d, j) order (a sequential scan with strict <: lowest index on ties; a NaN or +inf
+ * distance never wins): dist2 (batch, n, 3), idx (batch, n, 3) int32; unfilled slots (m < 3, non-finite
+ * candidates) hold (+inf, 0).  weight (batch, n, 3) or NULL: w_i = r_i / ((r_0 + r_1) + r_2) with
+ * r_i = 1 / (sqrt(d2_i) + 1e-8f) (correctly rounded sqrt and divisions; an unfilled slot gives 0, m = 1
+ * gives exactly [1, 0, 0], three unfilled slots NaN).
+ * lidar_three_interpolate_f32: out[b*n + i] = [(w0 f[i0] + w1 f[i1]) + w2 f[i2] (c2 columns, f =
+ * known_feat rows (batch*m rows of stride ldk) of frame b), skip[b*n + i] (c1 columns, row stride lds;
+ * NULL when c1 = 0), zeros to ldo]; out rows [batch*n, rows) are zeroed, so out is directly the A operand
+ * of lidar_dense_x3f_f32 / lidar_dense_f32 (as lidar_sa_group_rows_f32).  ldo % 4 == 0, ldo >= c1 + c2,
+ * rows >= batch*n; idx entries must lie in [0, m).
+ * lidar_row_argmax_f32: out[r] = argmax over c < C of x[r*ldx + c] as int32: lowest index on ties, a NaN
+ * counts as the maximum (np.argmax). */
+int lidar_three_nn_f32(lidar_handle *h, const float *unknown, const float *known, int64_t batch, int64_t n,
+                       int64_t m, float *dist2, int32_t *idx, float *weight, void *stream);
+int lidar_three_interpolate_f32(lidar_handle *h, const float *known_feat, int64_t ldk, int32_t c2, const int32_t *idx,
+                                const float *weight, const float *skip, int64_t lds, int32_t c1, int64_t batch,
+                                int64_t n, int64_t m, float *out, int64_t rows, int64_t ldo, void *stream);
+int lidar_row_argmax_f32(lidar_handle *h, const float *x, int64_t rows, int64_t ldx, int32_t c, int32_t *out,
+                         void *stream);
+
 /* y (batch*m, ldy) columns [col0, col0+3) = xyz rows; columns [col0+3, ldy) zeroed —
  * builds group_all's input [feats, xyz, 0-pad] next to features already in y. */
 int lidar_concat_xyz_pad_f32(lidar_handle *h, const float *xyz, int64_t rows, float *y,

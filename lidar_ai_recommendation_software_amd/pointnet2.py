@@ -11,7 +11,10 @@ distances ``(dx*dx + dy*dy) + dz*dz`` with one rounding per operation;
 FPS starts at index 0 and breaks ties to the lowest index; ball query keeps the first
 ``nsample`` hits in index order; grouping is ``[xyz - centre, features]`` (use_xyz);
 each SA branch is a 3-layer shared MLP (conv1x1 + folded BN + ReLU) max-pooled over
-its neighbourhood; the last level is group_all.
+its neighbourhood; the last level is group_all.  The decoder (feature propagation): three_nn keeps
+the three nearest coarse points in (distance, index) order, three_interpolate mixes their features
+with inverse-distance weights, the fine level's features are concatenated and a shared MLP follows
+per level; PointNet2Segmenter adds a per-point head and argmax.
 
 Layouts: xyz (B, N, 3) float32; features channels-last (B, N, C) float32.
 """
@@ -669,6 +672,217 @@ def dense_h3p(a, a_exp, wpack, b, cout, mode, bounds=(0.0, 0.0), relu=True, pool
     return (out, oexp) if mode == 1 else out
 
 
+# --------------------------------------------------- feature propagation (the decoder's operators)
+def _rows_check(t, what, rows, cols):
+    """t: a CUDA float32 (rows..., >= cols) tensor whose rows have one stride and unit column stride
+    (a column slice of padded rows is fine); returns the row stride."""
+    if t.dtype != torch.float32 or not t.is_cuda or t.dim() not in (2, 3) or (t.shape[-1] > 1 and t.stride(-1) != 1):
+        raise ValueError(f"{what} must be a CUDA float32 tensor of rows with unit column stride")
+    shape = (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+    stride = (0,) + tuple(t.stride()) if t.dim() == 2 else tuple(t.stride())
+    # the stride of a dimension of size 1 is arbitrary: the rows' stride is the first that is not
+    if shape[1] > 1:
+        ld = stride[1]
+    else:
+        ld = stride[0] if shape[0] > 1 else shape[2]
+    if shape[0] > 1 and shape[1] > 1 and stride[0] != shape[1] * ld:
+        raise ValueError(f"{what}: the frames' rows must share one stride")
+    if shape[0] * shape[1] != rows or shape[2] < cols or ld < shape[2]:
+        raise ValueError(f"{what}: expected {rows} rows of at least {cols} columns, got {tuple(t.shape)}")
+    return ld
+
+
+THREE_NN_CHUNK = 2048  # csrc/feature_prop.hip NN_CH: known points staged in LDS at a time
+THREE_NN_WIDE_MIN = 1 << 19  # B * n from which a thread owns four unknown points instead of two
+
+
+def three_nn(unknown, known, weights=True, slot=0):
+    """unknown (B, n, 3), known (B, m, 3) float32 CUDA -> (dist2 (B, n, 3), idx (B, n, 3) int32[, weight
+    (B, n, 3)]): per unknown point the three nearest known points of its frame in (distance, index)
+    order (exact fp32 (dx*dx + dy*dy) + dz*dz, lowest index on ties; a NaN or +inf distance never wins;
+    unfilled slots hold (+inf, 0)) and the inverse-distance weights r_i / ((r_0 + r_1) + r_2), r_i = 1 /
+    (sqrt(d2_i) + 1e-8).  m >= 1: one known point gives the weights [1, 0, 0]."""
+    _dev_check(unknown, known)
+    for t, what in ((unknown, "unknown"), (known, "known")):
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"three_nn: {what} must be (B, n, 3) float32")
+    B, n, _ = unknown.shape
+    m = known.shape[1]
+    if known.shape[0] != B or n < 1 or m < 1:
+        raise ValueError(f"three_nn: unknown {tuple(unknown.shape)} and known {tuple(known.shape)} must share B, "
+                         "with n >= 1 and m >= 1")
+    dev = unknown.device
+    d2 = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, n, 3), dtype=torch.int32, device=dev)
+    w = torch.empty((B, n, 3), dtype=torch.float32, device=dev) if weights else None
+    nat.call("lidar_three_nn_f32", nat.handle(dev.index, slot), nat.ptr(unknown), nat.ptr(known), B, n, m,
+             nat.ptr(d2), nat.ptr(idx), nat.ptr(w), nat.stream_ptr())
+    return (d2, idx, w) if weights else (d2, idx)
+
+
+def three_interpolate(known_feats, idx, weight, skip=None, out=None, slot=0):
+    """known_feats (B, m, c2), idx / weight (B, n, 3) (three_nn), skip (B, n, c1) or None -> rows
+    [(w0 f[i0] + w1 f[i1]) + w2 f[i2] | skip | 0-pad]: out (R, ldo) float32 contiguous with R >= B n and
+    ldo % 4 == 0, ldo >= c2 + c1 (default: R = B n rounded up to 128, ldo = c2 + c1 rounded up to 16 —
+    the dense GEMMs' A operand); rows past B n are zeroed.  known_feats and skip may be column slices of
+    wider rows (unit column stride, one row stride)."""
+    _dev_check(idx, weight, out)
+    if idx.dim() != 3 or idx.shape[2] != 3 or idx.dtype != torch.int32 or weight.dtype != torch.float32 \
+            or tuple(weight.shape) != tuple(idx.shape):
+        raise ValueError("three_interpolate: idx (B, n, 3) int32 and weight (B, n, 3) float32 expected")
+    B, n, _ = idx.shape
+    if known_feats.dim() != 3 or known_feats.shape[0] != B:
+        raise ValueError("three_interpolate: known_feats must be (B, m, c2)")
+    m, c2 = known_feats.shape[1], known_feats.shape[2]
+    if n < 1 or m < 1 or c2 < 1:
+        raise ValueError("three_interpolate: n, m and c2 must be at least 1")
+    ldk = _rows_check(known_feats, "three_interpolate: known_feats", B * m, c2)
+    c1, lds = 0, 0
+    if skip is not None:
+        if skip.dim() != 3 or skip.shape[0] != B or skip.shape[1] != n:
+            raise ValueError("three_interpolate: skip must be (B, n, c1)")
+        c1 = skip.shape[2]
+        lds = _rows_check(skip, "three_interpolate: skip", B * n, c1) if c1 else 0
+    dev = idx.device
+    if out is None:
+        out = torch.empty(((B * n + 127) // 128 * 128, (c2 + c1 + 15) // 16 * 16), dtype=torch.float32, device=dev)
+    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] < B * n or out.shape[1] % 4 \
+            or out.shape[1] < c1 + c2:
+        raise ValueError(f"three_interpolate: out must be (>= {B * n}, ldo) float32 with ldo % 4 == 0 and "
+                         f"ldo >= {c1 + c2}, got {tuple(out.shape)}")
+    nat.call("lidar_three_interpolate_f32", nat.handle(dev.index, slot), nat.ptr(known_feats), ldk, c2, nat.ptr(idx),
+             nat.ptr(weight), nat.ptr(skip) if c1 else None, lds, c1, B, n, m, nat.ptr(out), out.shape[0],
+             out.shape[1], nat.stream_ptr())
+    return out
+
+
+def row_argmax(x, c, out=None, slot=0):
+    """x (rows, >= c) float32 with unit column stride -> (rows,) int32: argmax over the first c columns,
+    lowest index on ties, a NaN counts as the maximum (np.argmax)."""
+    if x.dim() != 2 or c < 1:
+        raise ValueError("row_argmax: x must be (rows, >= c) with c >= 1")
+    ldx = _rows_check(x, "row_argmax: x", x.shape[0], c)
+    if out is None:
+        out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
+    _dev_check(out)
+    if out.dtype != torch.int32 or out.numel() != x.shape[0]:
+        raise ValueError("row_argmax: out must be (rows,) int32")
+    nat.call("lidar_row_argmax_f32", nat.handle(x.device.index, slot), nat.ptr(x), x.shape[0], ldx, int(c),
+             nat.ptr(out), nat.stream_ptr())
+    return out
+
+
+# ----------------------------------------------------------------- decoder configuration and weights
+# Feature-propagation MLPs, deepest level first (one per encoder level), then the head's hidden layers;
+# the input widths follow from the encoder configuration (fp_input_widths), so it serves SSG and MSG.
+FP_SSG = {"mlps": [[256, 256], [256, 128], [128, 128, 128]], "head": [128]}
+
+
+def level_channels(cfg):
+    """Feature channels of the encoder's point sets P_0 (the input frame: 0) .. P_L (the last level's output)."""
+    return [0] + [sum(w[-1] for w in lvl["mlps"]) for lvl in cfg["levels"]]
+
+
+def fp_input_widths(cfg, fp_cfg):
+    """Per FP level (deepest first) (c2, c1): the channels interpolated from the coarser set and the skip
+    channels of the finer one.  Level i propagates P_(L-i) onto P_(L-i-1)."""
+    ch = level_channels(cfg)
+    L = len(cfg["levels"])
+    if len(fp_cfg["mlps"]) != L:
+        raise ValueError(f"fp_cfg: {len(fp_cfg['mlps'])} FP levels, the encoder has {L} levels")
+    out, c2 = [], ch[L]
+    for i, widths in enumerate(fp_cfg["mlps"]):
+        if not widths:
+            raise ValueError(f"fp_cfg level {i}: an FP level needs at least one layer")
+        out.append((c2, ch[L - i - 1]))
+        c2 = widths[-1]
+    return out
+
+
+def _fp_layer_dims(cfg, fp_cfg, num_classes):
+    """[(name, [(cin, cout) per layer])]: the FP levels ("fp<i>"), then "head" (its hidden layers and the
+    classifier)."""
+    if num_classes < 1:
+        raise ValueError("num_classes must be at least 1")
+    dims = []
+    for i, ((c2, c1), widths) in enumerate(zip(fp_input_widths(cfg, fp_cfg), fp_cfg["mlps"])):
+        cin, lay = c2 + c1, []
+        for cout in widths:
+            lay.append((cin, cout))
+            cin = cout
+        dims.append((f"fp{i}", lay))
+    lay = []
+    for cout in list(fp_cfg["head"]) + [num_classes]:
+        lay.append((cin, cout))
+        cin = cout
+    dims.append(("head", lay))
+    return dims
+
+
+def init_fp_weights(cfg, fp_cfg=FP_SSG, num_classes=2, seed=0):
+    """Deterministic random init of the decoder (as init_weights: U(-1/sqrt(cin), 1/sqrt(cin)), BN folded at
+    its identity).  Returns {"fp": [level][layer] = (W (cin, cout), b), "head": [layer] = (W, b)}: an FP
+    level's rows are [interpolated (c2), skip (c1)]; the head's last layer is the classifier (no ReLU)."""
+    rng = np.random.default_rng(seed)
+    out = {"fp": [], "head": []}
+    for name, lay in _fp_layer_dims(cfg, fp_cfg, num_classes):
+        layers = []
+        for cin, cout in lay:
+            bound = 1.0 / np.sqrt(cin)
+            layers.append((rng.uniform(-bound, bound, (cin, cout)).astype(np.float32),
+                           rng.uniform(-bound, bound, cout).astype(np.float32)))
+        if name == "head":
+            out["head"] = layers
+        else:
+            out["fp"].append(layers)
+    return out
+
+
+def check_fp_weights(cfg, fp_cfg, num_classes, fp_weights):
+    """Validate {"fp": [level][layer], "head": [layer]} = (W (cin, cout), b (cout,)) against the widths cfg,
+    fp_cfg and num_classes give; returns them as contiguous float32 arrays.  Raises ValueError naming the
+    first mismatch."""
+    dims = _fp_layer_dims(cfg, fp_cfg, num_classes)
+    if not isinstance(fp_weights, dict) or "fp" not in fp_weights or "head" not in fp_weights:
+        raise ValueError("fp_weights must be a dict with the keys 'fp' and 'head'")
+    if len(fp_weights["fp"]) != len(dims) - 1:
+        raise ValueError(f"fp_weights: {len(fp_weights['fp'])} FP levels, the configuration has {len(dims) - 1}")
+    out = {"fp": [], "head": []}
+    for (name, lay), layers in zip(dims, list(fp_weights["fp"]) + [fp_weights["head"]]):
+        if len(layers) != len(lay):
+            raise ValueError(f"fp_weights {name}: {len(layers)} layers, expected {len(lay)}")
+        conv = []
+        for j, ((cin, cout), (W, b)) in enumerate(zip(lay, layers)):
+            W = np.ascontiguousarray(W, dtype=np.float32)
+            b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+            if W.shape != (cin, cout) or b.shape != (cout,):
+                raise ValueError(f"fp_weights {name} layer {j}: W {W.shape}, b {b.shape}; "
+                                 f"expected ({cin}, {cout}) and ({cout},)")
+            conv.append((W, b))
+        if name == "head":
+            out["head"] = conv
+        else:
+            out["fp"].append(conv)
+    return out
+
+
+def save_fp_weights(path, fp_weights):
+    """Decoder weights to an .npz of plain arrays (keys fp<level>_<layer>_{W,b}, head_<layer>_{W,b})."""
+    arrs = {f"fp{i}_{j}_{k}": a for i, layers in enumerate(fp_weights["fp"]) for j, wb in enumerate(layers)
+            for k, a in zip("Wb", wb)}
+    arrs.update({f"head_{j}_{k}": a for j, wb in enumerate(fp_weights["head"]) for k, a in zip("Wb", wb)})
+    np.savez(path, **arrs)
+
+
+def load_fp_weights(path, cfg, fp_cfg=FP_SSG, num_classes=2):
+    """The .npz save_fp_weights wrote (loaded with allow_pickle=False), validated by check_fp_weights."""
+    with np.load(path, allow_pickle=False) as z:
+        w = {"fp": [[(z[f"fp{i}_{j}_W"], z[f"fp{i}_{j}_b"]) for j in range(len(widths))]
+                    for i, widths in enumerate(fp_cfg["mlps"])],
+             "head": [(z[f"head_{j}_W"], z[f"head_{j}_b"]) for j in range(len(fp_cfg["head"]) + 1)]}
+    return check_fp_weights(cfg, fp_cfg, num_classes, w)
+
+
 # ----------------------------------------------------------------------- backbone
 class _Timers:
     """Optional per-launch HIP-event timing on the launching stream (bench.py): per kernel name
@@ -928,6 +1142,159 @@ class PointNet2Backbone:
         h2 = _call(t, "sa3_dense2", B, dense_relu, h1, ws[1], bs[1])
         out = torch.zeros((rows // M, ws[2].shape[1]), dtype=torch.float32, device=x.device)
         return _call(t, "sa3_dense3_pool", B, dense_relu, h2, ws[2], bs[2], pool_rows=M, out=out)
+
+    __call__ = forward
+
+
+# ---------------------------------------------------------------------- segmentation
+class PointNet2Segmenter:
+    """PointNet++ per-point segmentation on liblidar_amd: a PointNet2Backbone, its feature-propagation
+    decoder (three_nn -> three_interpolate -> shared MLP per level, deepest first) and a per-point head
+    (ReLU layers, then a linear classifier).  ``forward(xyz)`` -> logits (B, N, num_classes);
+    ``segment(xyz)`` -> labels (B, N) int32 (argmax, lowest class on ties)."""
+
+    def __init__(self, cfg=SSG, fp_cfg=FP_SSG, num_classes=2, weights=None, fp_weights=None, device="cuda", seed=0,
+                 x3=True):
+        """weights / fp_weights: the encoder's (init_weights layout) and the decoder's (init_fp_weights
+        layout); default: their deterministic random init from `seed`.  x3=True runs the decoder's layers
+        in h3 arithmetic on the fp16 matrix cores (lidar_dense_x3f_f32), x3=False on the native fp32 ones
+        (lidar_dense_f32), as the backbone's MLPs."""
+        self.backbone = PointNet2Backbone(cfg, weights=weights, device=device, seed=seed, x3=x3)
+        self.cfg, self.fp_cfg, self.num_classes = cfg, fp_cfg, int(num_classes)
+        self.device, self.x3 = self.backbone.device, bool(x3)
+        self.fp_weights = (check_fp_weights(cfg, fp_cfg, num_classes, fp_weights) if fp_weights is not None
+                           else init_fp_weights(cfg, fp_cfg, num_classes, seed))
+        self.fp = []
+        cp = 0
+        for (c2, c1), layers in zip(fp_input_widths(cfg, fp_cfg), self.fp_weights["fp"]):
+            ldo = (c2 + c1 + 15) // 16 * 16  # the interpolated rows' stride: k of the level's first GEMM
+            lay = self._layers(layers, ldo, [True] * len(layers))
+            self.fp.append({"c2": c2, "c1": c1, "ldo": ldo, "layers": lay, "cout": layers[-1][0].shape[1]})
+            cp = lay[-1]["cout"]
+        head = self.fp_weights["head"]
+        self.head = self._layers(head, cp, [True] * (len(head) - 1) + [False])  # the classifier: no ReLU
+
+    def _layers(self, layers, kin, relus):
+        """Device operands of consecutive dense layers in pad_layer's layout (rows padded to the width of
+        what feeds them, columns to a multiple of 128), packed once for the h3 GEMM."""
+        out = []
+        for (w, b), relu in zip(layers, relus):
+            wp, bp = pad_layer(w, b, kin)
+            wd = torch.from_numpy(wp).to(self.device)
+            lay = {"w": wd, "b": torch.from_numpy(bp).to(self.device), "cout": wp.shape[1], "relu": relu}
+            if self.x3:
+                lay["packed"] = pack_dense_x3(wd)
+            out.append(lay)
+            kin = wp.shape[1]
+        return out
+
+    def _dense(self, a, lay):
+        if self.x3:
+            return dense_x3s(a, lay["packed"], lay["b"], lay["cout"], relu=lay["relu"])
+        return dense(a, lay["w"], lay["b"], relu=lay["relu"])
+
+    def point_sets(self, xyz, levels, global_feat):
+        """[(xyz, features or None)] of P_0 (the frame) .. P_L from forward(keep_levels=True)'s output: a
+        group_all level is one point (at the origin: with one known point the weights are [1, 0, 0]
+        wherever it lies) carrying the global feature."""
+        sets = [(xyz, None)] + [(lv[0], lv[1]) for lv in levels]
+        if self.cfg["levels"][-1].get("group_all"):
+            B = xyz.shape[0]
+            sets.append((torch.zeros((B, 1, 3), dtype=torch.float32, device=xyz.device),
+                         global_feat.reshape(B, 1, -1)))
+        if len(sets) != len(self.cfg["levels"]) + 1:
+            raise ValueError(f"decode: {len(levels)} encoder levels given, the configuration has "
+                             f"{len(self.cfg['levels'])}")
+        return sets
+
+    def _frame_bytes(self, sets):
+        """Upper estimate of one frame's live decoder activations: per level its padded rows and two layer
+        outputs."""
+        L = len(self.fp)
+        need = 0
+        for i, fp in enumerate(self.fp):
+            n = sets[L - i - 1][0].shape[1]
+            wide = max(lay["cout"] for lay in fp["layers"] + (self.head if i == L - 1 else []))
+            need = max(need, n * 4 * (fp["ldo"] + 2 * wide))
+        return need
+
+    def decode(self, xyz, levels, global_feat, keep_levels=False, max_bytes=1 << 30):
+        """The decoder on an encoder pass: xyz (B, N, 3), levels = per SA level (new_xyz (B, M, 3),
+        features (B, M, C), ...) and global_feat (B, C) as PointNet2Backbone.forward(xyz,
+        keep_levels=True) returns them.  -> logits (B, N, num_classes); with keep_levels also {"fp": per FP
+        level (deepest first) {"rows": the interpolated rows [interp | skip] (B, n, c2 + c1), "idx",
+        "weight", "feats": the level's output (B, n, cout)}, "head": the head's last hidden layer
+        (B, N, c)}.  Frames run in chunks whose activations stay under max_bytes (every operator is per
+        frame: the chunking does not change a bit)."""
+        sets = self.point_sets(xyz, levels, global_feat)
+        _dev_check(xyz)
+        B, N, _ = xyz.shape
+        nc = self.num_classes
+        logits = torch.empty((B, N, nc), dtype=torch.float32, device=xyz.device)
+        fc = max(1, min(B, max_bytes // max(1, self._frame_bytes(sets))))
+        # the neighbours depend on the point sets alone (36 bytes per point): one launch per level over the
+        # whole batch, ahead of the chunks
+        t, L = self.backbone.timers, len(self.fp)
+        nn = [_call(t, f"fp{i}_three_nn", B, three_nn, sets[L - i - 1][0], sets[L - i][0])[1:] for i in range(L)]
+        kept = []
+        for b0 in range(0, B, fc):
+            part = [(x[b0:b0 + fc], f[b0:b0 + fc] if f is not None else None) for x, f in sets]
+            a, k = self._decode_frames(part, [(i[b0:b0 + fc], w[b0:b0 + fc]) for i, w in nn], keep_levels)
+            nb = part[0][0].shape[0]
+            logits[b0:b0 + nb] = a[:nb * N, :nc].view(nb, N, nc)
+            kept.append(k)
+        if not keep_levels:
+            return logits
+        cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, dim=0)
+        out = {"fp": [{key: cat([k["fp"][i][key] for k in kept]) for key in kept[0]["fp"][i]}
+                      for i in range(len(self.fp))],
+               "head": cat([k["head"] for k in kept])}
+        return logits, out
+
+    def _decode_frames(self, sets, nn, keep):
+        """Every FP level and the head on the frames of `sets` (nn: per FP level their three_nn (idx, weight));
+        -> (the classifier's padded rows (R, 128 k), what decode() keeps)."""
+        t = self.backbone.timers
+        L = len(self.fp)
+        kxyz, kfeat = sets[L]
+        kept = {"fp": [], "head": None}
+        a = None
+        for i, fp in enumerate(self.fp):
+            uxyz, skip = sets[L - i - 1]
+            nb, n, _ = uxyz.shape
+            c2, c1 = fp["c2"], fp["c1"]
+            if kfeat.shape[2] != c2 or (c1 and (skip is None or skip.shape[2] != c1)):
+                raise ValueError(f"decode: FP level {i} expects {c2} coarse and {c1} skip channels")
+            idx, w = nn[i]
+            rows = torch.empty(((nb * n + 127) // 128 * 128, fp["ldo"]), dtype=torch.float32, device=uxyz.device)
+            _call(t, f"fp{i}_interpolate", nb, three_interpolate, kfeat, idx, w, skip if c1 else None, rows)
+            a = rows
+            for j, lay in enumerate(fp["layers"]):
+                a = _call(t, f"fp{i}_dense{j + 1}", nb, self._dense, a, lay)
+            feats = a[:nb * n].view(nb, n, a.shape[1])[..., :fp["cout"]]
+            if keep:
+                kept["fp"].append({"rows": rows[:nb * n].view(nb, n, fp["ldo"])[..., :c2 + c1], "idx": idx, "weight": w,
+                                   "feats": feats})
+            kxyz, kfeat = uxyz, feats
+        nb, n, _ = kxyz.shape
+        for j, lay in enumerate(self.head):
+            if keep and j == len(self.head) - 1:
+                kept["head"] = a[:nb * n].view(nb, n, a.shape[1])[..., :self.fp_weights["head"][-1][0].shape[0]]
+            a = _call(t, f"head_dense{j + 1}", nb, self._dense, a, lay)
+        return a, kept
+
+    def forward(self, xyz, max_bytes=1 << 30):
+        """xyz (B, N, 3) float32 CUDA -> logits (B, N, num_classes): the encoder pass with its levels kept,
+        then decode()."""
+        g, levels = self.backbone.forward(xyz, keep_levels=True)
+        return self.decode(xyz, levels, g, max_bytes=max_bytes)
+
+    def segment(self, xyz, max_bytes=1 << 30):
+        """-> labels (B, N) int32: the argmax of forward()'s logits over the classes (lowest class on ties,
+        a NaN counts as the maximum)."""
+        logits = self.forward(xyz, max_bytes=max_bytes)
+        B, N, nc = logits.shape
+        return row_argmax(logits.view(B * N, nc), nc).view(B, N)
 
     __call__ = forward
 
