@@ -33,6 +33,8 @@
 // layer-3 rule, sa_mlp_x3.hip), from the input row's own exponent (PL) or its running one (fp32 A).
 #include "h3.hpp"
 
+int lidar_dense_x3_packed_image(int32_t k, int32_t cout, int64_t *bytes);  // x3_pack.hip
+
 namespace {
 
 using lidar_h3::f16x8;
@@ -358,9 +360,48 @@ __global__ __launch_bounds__(256, 2) void dense_x3_kernel(const float *__restric
     }
 }
 
-}  // namespace
+// The tail both entry points share, reported under the caller's name `fn`: the output checks, the
+// launch geometry, the image's exponent word and the kernel for (mode, x1, planes).  a_exp non-null:
+// A is h3 planes a_plane halves apart.
+int launch_dense_x3(const char *fn, lidar_handle *h, const float *a, int32_t lda, int64_t rows, int32_t k,
+                    const int32_t *a_exp, int64_t a_plane, const void *packed, const float *bias, int32_t cout,
+                    int32_t mode, bool x1, int32_t relu_on, int32_t pool_rows, float *out, int32_t *out_exp,
+                    int64_t ldo, float w_colsum, float b_max, void *stream)
+{
+    REQUIRE(ldo >= cout && ldo % 4 == 0, std::string(fn) + ": ldo must be >= cout and a multiple of 4");
+    REQUIRE(mode != 2 || (relu_on && pool_rows > 0 && pool_rows % SBM == 0 && rows % pool_rows == 0),
+            std::string(fn) + ": the max-pool needs relu and pool_rows a multiple of 128 dividing rows");
+    if (rows == 0) return LIDAR_OK;
+    ON_DEVICE(h->device);
+    const int ks = (k + 31) / 32 * 2;  // the packed image of a (k, cout) layer covers ceil(k/32)*2 k-steps
+    const int ntn = cout / SBN;
+    const int64_t total = (rows / SBM) * ntn, per_xcd = (total + 7) / 8;
+    REQUIRE(per_xcd * 8 <= 0x7fffffff, std::string(fn) + ": too many rows");
+    int64_t wbytes = 0;
+    if (lidar_dense_x3_packed_image(k, cout, &wbytes) != LIDAR_OK) return LIDAR_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint16_t *w = static_cast<const uint16_t *>(packed);
+    // the h3 image ends in its layer scaling exponent (x3_pack.hip)
+    const int32_t *wexp = reinterpret_cast<const int32_t *>(static_cast<const char *>(packed) + wbytes);
+    const dim3 grid((unsigned)(per_xcd * 8)), block(256);
+    const int rl = relu_on ? 1 : 0;
+    auto go = [&](auto kern, int relu, int pool) {
+        hipLaunchKernelGGL(kern, grid, block, 0, s, a, (int)lda, w, ks, wexp, bias, relu, pool, out, ldo, (int)cout, ntn,
+                           total, per_xcd, (int)k, a_exp, a_plane, out_exp, w_colsum, b_max);
+    };
+    const bool pl = a_exp != nullptr;
+    if (x1) go(dense_x3_kernel<0, true>, rl, 0);
+    else if (!pl && mode == 0) go(dense_x3_kernel<0, false>, rl, 0);
+    else if (!pl && mode == 2) go(dense_x3_kernel<2, false>, 1, (int)pool_rows);
+    else if (pl && mode == 0) go(dense_x3_kernel<0, false, true>, rl, 0);
+    else if (pl && mode == 1) go(dense_x3_kernel<1, false, true>, rl, 0);
+    else if (pl) go(dense_x3_kernel<2, false, true>, 1, (int)pool_rows);
+    else go(dense_x3_kernel<1, false>, rl, 0);  // fp32 rows in, h3 planes out
+    LAUNCH_CHECK();
+    return LIDAR_OK;
+}
 
-int lidar_dense_x3_packed_image(int32_t k, int32_t cout, int64_t *bytes);  // x3_pack.hip
+}  // namespace
 
 // the GEMM with A as fp32 rows (rows, lda) (split inside the tile loop; elements k..lda-1 are
 // never read: a stage's chunks at or past k re-read its first chunk, whose weights there are zero —
@@ -382,33 +423,8 @@ LIDAR_EXPORT int lidar_dense_x3f_f32(lidar_handle *h, const float *a, int32_t ld
             "lidar_dense_x3f_f32: rows % 128, k <= lda, cout % 128 must hold");
     REQUIRE(k % 4 == 0 && lda % 4 == 0, "lidar_dense_x3f_f32: k % 4 == 0 and lda % 4 == 0 (fp32 rows)");
     REQUIRE(mode == 0 || mode == 2, "lidar_dense_x3f_f32: mode must be 0 or 2");
-    REQUIRE(ldo >= cout && ldo % 4 == 0, "lidar_dense_x3f_f32: ldo must be >= cout and a multiple of 4");
-    REQUIRE(mode != 2 || (relu_on && pool_rows > 0 && pool_rows % SBM == 0 && rows % pool_rows == 0),
-            "lidar_dense_x3f_f32: the max-pool needs relu and pool_rows a multiple of 128 dividing rows");
-    if (rows == 0) return LIDAR_OK;
-    ON_DEVICE(h->device);
-    const int ks = (k + 31) / 32 * 2;  // the packed image of a (k, cout) layer covers ceil(k/32)*2 k-steps
-    const int ntn = cout / SBN;
-    const int64_t total = (rows / SBM) * ntn, per_xcd = (total + 7) / 8;
-    REQUIRE(per_xcd * 8 <= 0x7fffffff, "lidar_dense_x3f_f32: too many rows");
-    int64_t wbytes = 0;
-    if (lidar_dense_x3_packed_image(k, cout, &wbytes) != LIDAR_OK) return LIDAR_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint16_t *w = static_cast<const uint16_t *>(packed);
-    // the h3 image ends in its layer scaling exponent (x3_pack.hip)
-    const int32_t *wexp = reinterpret_cast<const int32_t *>(static_cast<const char *>(packed) + wbytes);
-    const dim3 grid((unsigned)(per_xcd * 8)), block(256);
-    auto go = [&](auto kern, int relu, int pool) {
-        hipLaunchKernelGGL(kern, grid, block, 0, s, a, (int)lda, w, ks, wexp, bias, relu, pool,
-                           static_cast<float *>(out), ldo, (int)cout, ntn, total, per_xcd, (int)k,
-                           (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr, 0.0f, 0.0f);
-    };
-    const int rl = relu_on ? 1 : 0;
-    if (x1) go(dense_x3_kernel<0, true>, rl, 0);
-    else if (mode == 0) go(dense_x3_kernel<0, false>, rl, 0);
-    else go(dense_x3_kernel<2, false>, 1, (int)pool_rows);
-    LAUNCH_CHECK();
-    return LIDAR_OK;
+    return launch_dense_x3("lidar_dense_x3f_f32", h, a, lda, rows, k, nullptr, 0, packed, bias, cout, mode, x1, relu_on,
+                           pool_rows, static_cast<float *>(out), nullptr, ldo, 0.0f, 0.0f, stream);
 }
 
 // The h3 chain of group_all: A as fp32 rows (a_exp NULL; lda % 4 == 0, elements k..lda-1 never
@@ -423,46 +439,15 @@ LIDAR_EXPORT int lidar_dense_h3p_f32(lidar_handle *h, const void *a, int32_t lda
                                      int32_t mode, int32_t relu_on, int32_t pool_rows, void *out, int32_t *out_exp,
                                      int64_t ldo, float w_colsum, float b_max, void *stream)
 {
-    const bool pl = a_exp != nullptr;
     REQUIRE(h && a && packed && bias && out, "lidar_dense_h3p_f32: null pointer");
     REQUIRE(rows % SBM == 0 && k > 0 && k <= lda && cout % SBN == 0 && cout > 0,
             "lidar_dense_h3p_f32: rows % 128, k <= lda, cout % 128 must hold");
-    REQUIRE(pl ? lda == (k + 31) / 32 * 32 : (k % 4 == 0 && lda % 4 == 0),
+    REQUIRE(a_exp != nullptr ? lda == (k + 31) / 32 * 32 : (k % 4 == 0 && lda % 4 == 0),
             "lidar_dense_h3p_f32: planes need lda = k rounded up to 32; fp32 rows k % 4 == 0 and lda % 4 == 0");
     REQUIRE(mode >= 0 && mode <= 2, "lidar_dense_h3p_f32: mode must be 0, 1 or 2");
     REQUIRE(mode != 1 || (out_exp != nullptr && ldo == cout && w_colsum >= 0.0f && b_max >= 0.0f),
             "lidar_dense_h3p_f32: mode 1 needs out_exp, ldo == cout and the bounds w_colsum, b_max >= 0");
-    REQUIRE(ldo >= cout && ldo % 4 == 0, "lidar_dense_h3p_f32: ldo must be >= cout and a multiple of 4");
-    REQUIRE(mode != 2 || (relu_on && pool_rows > 0 && pool_rows % SBM == 0 && rows % pool_rows == 0),
-            "lidar_dense_h3p_f32: the max-pool needs relu and pool_rows a multiple of 128 dividing rows");
-    if (rows == 0) return LIDAR_OK;
-    ON_DEVICE(h->device);
-    const int ks = (k + 31) / 32 * 2;
-    const int ntn = cout / SBN;
-    const int64_t total = (rows / SBM) * ntn, per_xcd = (total + 7) / 8;
-    REQUIRE(per_xcd * 8 <= 0x7fffffff, "lidar_dense_h3p_f32: too many rows");
-    int64_t wbytes = 0;
-    if (lidar_dense_x3_packed_image(k, cout, &wbytes) != LIDAR_OK) return LIDAR_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint16_t *w = static_cast<const uint16_t *>(packed);
-    const int32_t *wexp = reinterpret_cast<const int32_t *>(static_cast<const char *>(packed) + wbytes);
-    const dim3 grid((unsigned)(per_xcd * 8)), block(256);
-    const float *af = static_cast<const float *>(a);
-    float *o = static_cast<float *>(out);
-    const int rl = relu_on ? 1 : 0;
-    auto go = [&](auto kern, int relu, int pool) {
-        hipLaunchKernelGGL(kern, grid, block, 0, s, af, (int)lda, w, ks, wexp, bias, relu, pool, o, ldo, (int)cout, ntn,
-                           total, per_xcd, (int)k, a_exp, rows * lda, out_exp, w_colsum, b_max);
-    };
-    if (pl) {
-        if (mode == 0) go(dense_x3_kernel<0, false, true>, rl, 0);
-        else if (mode == 1) go(dense_x3_kernel<1, false, true>, rl, 0);
-        else go(dense_x3_kernel<2, false, true>, 1, (int)pool_rows);
-    } else {
-        if (mode == 0) go(dense_x3_kernel<0, false>, rl, 0);
-        else if (mode == 1) go(dense_x3_kernel<1, false>, rl, 0);
-        else go(dense_x3_kernel<2, false>, 1, (int)pool_rows);
-    }
-    LAUNCH_CHECK();
-    return LIDAR_OK;
+    return launch_dense_x3("lidar_dense_h3p_f32", h, static_cast<const float *>(a), lda, rows, k, a_exp, rows * lda,
+                           packed, bias, cout, mode, false, relu_on, pool_rows, static_cast<float *>(out), out_exp,
+                           ldo, w_colsum, b_max, stream);
 }

@@ -18,7 +18,7 @@
 // CU that also hosts an FPS workgroup (32-row tiles need ~256 and drop to 1 there).
 #include <vector>
 
-#include "common.hpp"
+#include "sa_shapes.hpp"
 
 namespace {
 
@@ -218,9 +218,8 @@ template <int C1, int C2, int C3, int NS, bool XYZ, int WPG>
 int launch16w(const float *p, int64_t stride, const float *q, const int32_t *idx, int64_t batch, int64_t n,
               int64_t m, const float *packed, float *out, int64_t os, int64_t oo, hipStream_t s)
 {
-    const int64_t total = batch * m;
-    const int64_t blocks = (total + WPG - 1) / WPG;
-    REQUIRE(blocks <= 0x7fffffff, "sa_group_mlp16: too many centres");
+    int64_t total, blocks;
+    if (int rc = lidar_sa::launch_geometry("sa_group_mlp16", batch, m, WPG, total, blocks)) return rc;
     hipLaunchKernelGGL((sa16_kernel<C1, C2, C3, NS, XYZ, WPG>), dim3((unsigned)blocks), dim3(64 * WPG), 0, s, p,
                        stride, q, idx, (int)n, (int)m, total, packed, out, os, oo);
     LAUNCH_CHECK();
@@ -245,22 +244,16 @@ LIDAR_EXPORT int64_t lidar_mlp_packed_size16(int32_t xyz_level, int32_t c1, int3
 }
 
 // host packer for the 16-row kernels: w1 (3 or 3 + cfeat rows, c1) is only read for an xyz
-// level (its first 3 rows: dx, dy, dz); w2 (c1, c2), w3 (c2, c3); biases b1, b2, b3
+// level (its first 3 rows: dx, dy, dz); w2 (c1, c2), w3 (c2, c3); biases b1, b2, b3.  The W1 lanes and the
+// biases are written by the helpers every packer shares (sa_shapes.hpp); the 16x16x4 k order is this file's own
 LIDAR_EXPORT int lidar_mlp_pack16_f32(int32_t xyz_level, int32_t c1, int32_t c2, int32_t c3, const float *w1,
                                       const float *b1, const float *w2, const float *b2, const float *w3,
                                       const float *b3, float *packed)
 {
     REQUIRE(b1 && w2 && b2 && w3 && b3 && packed && (!xyz_level || w1), "lidar_mlp_pack16_f32: null pointer");
-    REQUIRE(c1 % 32 == 0 && c2 % 32 == 0 && c3 % 32 == 0 && c1 > 0 && c2 > 0 && c3 > 0,
-            "lidar_mlp_pack16_f32: widths must be positive multiples of 32");
+    if (int rc = lidar_sa::check_pack_widths("lidar_mlp_pack16_f32", c1, c2, c3)) return rc;
     float *o = packed;
-    if (xyz_level) {
-        for (int t = 0; t < c1 / 16; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int qq = l >> 4;
-                *o++ = qq < 3 ? w1[(int64_t)qq * c1 + 16 * t + (l & 15)] : 0.0f;
-            }
-    }
+    if (xyz_level) o = lidar_sa::write_w1_lanes(o, w1, c1);
     auto layer = [&](const float *w, int cin, int cout) {
         const int steps = cin / 4;
         for (int c = 0; c < cout / 32; ++c)
@@ -275,9 +268,7 @@ LIDAR_EXPORT int lidar_mlp_pack16_f32(int32_t xyz_level, int32_t c1, int32_t c2,
     };
     layer(w2, c1, c2);
     layer(w3, c2, c3);
-    for (int i = 0; i < c1; ++i) *o++ = b1[i];
-    for (int i = 0; i < c2; ++i) *o++ = b2[i];
-    for (int i = 0; i < c3; ++i) *o++ = b3[i];
+    lidar_sa::write_biases(o, b1, c1, b2, c2, b3, c3);
     return LIDAR_OK;
 }
 
@@ -289,23 +280,18 @@ LIDAR_EXPORT int lidar_sa_group_mlp16_f32(lidar_handle *h, int32_t xyz_level, co
                                           int32_t nsample, int32_t c1, int32_t c2, int32_t c3, const float *packed,
                                           float *out, int64_t out_stride, int64_t out_offset, void *stream)
 {
-    REQUIRE(h && p && q && idx && packed && out, "lidar_sa_group_mlp16_f32: null pointer");
-    REQUIRE(batch >= 0 && n >= 1 && m >= 1, "lidar_sa_group_mlp16_f32: bad sizes");
-    REQUIRE(xyz_level || (p_stride >= c1 && p_stride % 4 == 0), "lidar_sa_group_mlp16_f32: bad p_stride");
-    REQUIRE(out_offset >= 0 && out_offset + c3 <= out_stride, "lidar_sa_group_mlp16_f32: output columns exceed out_stride");
+    if (int rc = lidar_sa::check_args("lidar_sa_group_mlp16_f32", h && p && q && idx && packed && out,
+                                      batch >= 0 && n >= 1 && m >= 1,
+                                      xyz_level || (p_stride >= c1 && p_stride % 4 == 0), out_offset, c3, out_stride))
+        return rc;
     if (batch == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define LIDAR_SA16(C1_, C2_, C3_, NS_, X_)                                                                 \
+#define LIDAR_SA16(C1_, C2_, C3_, NS_, X_, LEAN_)                                                          \
     if (!!xyz_level == X_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                         \
         return launch16<C1_, C2_, C3_, NS_, X_>(p, p_stride, q, idx, batch, n, m, packed, out, out_stride, \
                                                 out_offset, s);
-    LIDAR_SA16(64, 64, 128, 32, true)
-    LIDAR_SA16(32, 32, 64, 16, true)
-    LIDAR_SA16(128, 128, 256, 64, false)
-    LIDAR_SA16(128, 128, 256, 128, false)
-    LIDAR_SA16(64, 64, 128, 32, false)
-    LIDAR_SA16(64, 96, 128, 128, true)
+    LIDAR_SA_SHAPES(LIDAR_SA16)
 #undef LIDAR_SA16
     return lidar::fail(LIDAR_EINVAL, "lidar_sa_group_mlp16_f32: unsupported (widths, nsample) combination");
 }

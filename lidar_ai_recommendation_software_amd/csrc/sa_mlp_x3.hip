@@ -6,8 +6,8 @@
 // then unscaled once (exact): <= ~3 2^-22 |a*b| per product, fp32-class, so the features meet
 // 1e-4 RELATIVE on every element >= 1e-2 RMS (tests/test_gpu_tier_n.py).  Weights are scaled per
 // layer at pack time; activations per 16-row tile: layer 2's input by its tile maximum, layer 3's
-// by the tile maximum (fused SA1 kernel) or by the bound colsum(W2) 2^e2 + max|b2| (lean SA2
-// kernel, which splits layer 2's output chunk by chunk).  fp16 x fp16 products are exact in fp32.
+// by the bound colsum(W2) 2^e2 + max|b2| (no pass over the tile; the lean SA2 kernel splits
+// layer 2's output chunk by chunk).  fp16 x fp16 products are exact in fp32.
 // The fp16 MFMA issues 16x the fp32 one's flops per cycle, so three of them still run ~5x the
 // fp32 rate.  X1 (the bf16 spec, BASELINE configs[4]) runs one bf16 product per MFMA instead.
 //
@@ -26,6 +26,7 @@
 
 #include "bq_grid.hpp"
 #include "h3.hpp"
+#include "sa_shapes.hpp"
 
 namespace {
 
@@ -129,12 +130,6 @@ __device__ __forceinline__ float max_row_groups(float v)
 // full-chip query launch competes with the pipeline; out_idx (optional) receives the indices.
 #ifndef LIDAR_BQ_CAP
 #define LIDAR_BQ_CAP 512
-#endif
-// LIDAR_SA_E3_BOUND: layer 3's input exponent in sa_x3_kernel from the bound colsum(W2) 2^e2 + max|b2|
-// (1, round 4: no pass over the tile, 95 VGPRs and no scratch; SA1 1.66 -> 1.62 ms alone per 128
-// frames) or a wave maximum over the tile (0)
-#ifndef LIDAR_SA_E3_BOUND
-#define LIDAR_SA_E3_BOUND 1
 #endif
 // LIDAR_SA1_W: waves per SIMD the fused SA1 kernel (NS = 32, fp32 contract) is built for (A/B builds only)
 #ifndef LIDAR_SA1_W
@@ -375,18 +370,9 @@ __global__ __launch_bounds__(256, (BQ && !X1 && NS == 32) ? LIDAR_SA1_W : (R == 
                     for (int rr = 0; rr < R; ++rr) {
                         float sc = 1.0f;
                         if constexpr (!X1) {
-#if LIDAR_SA_E3_BOUND
                             // scaled by the bound colsum(W2) 2^e2 + max|b2| (the lean kernel's rule): no
                             // pass over the tile
                             e3[rr] = bound_exp3(*reinterpret_cast<const X3Tail *>(Bias + C1 + C2 + C3), e2[rr]);
-#else
-                            uint32_t mb = 0;  // scaled by the tile's maximum
-#pragma unroll
-                            for (int t = 0; t < T2; ++t)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) mb = max(mb, __float_as_uint(y2[rr][t][r]));  // ReLU outputs: non-negative bits, or a NaN (its centre is NaN whatever the scale)
-                            e3[rr] = lidar_h3::wave_exp(mb);
-#endif
                             sc = lidar_h3::scale_of(e3[rr]);
                         }
 #pragma unroll
@@ -682,50 +668,51 @@ constexpr int rows_for()
     return X1 && NS >= 16 * LIDAR_X1_ROWS ? LIDAR_X1_ROWS : (NS >= 16 * LIDAR_X3_ROWS ? LIDAR_X3_ROWS : 1);
 }
 
-template <int C1, int C2, int C3, int NS>
-int launch_x3_lean(const float *p, int64_t stride, const float *q, const int32_t *idx, int64_t batch, int64_t n,
-                   int64_t m, const void *packed, float *out, int64_t os, int64_t oo, hipStream_t s)
-{
-    const int64_t total = batch * m;
-    const int64_t blocks = (total + 3) / 4;
-    REQUIRE(blocks <= 0x7fffffff, "sa_group_mlp_x3: too many centres");
-    // a centre's row indices in one coalesced load whenever NS is a multiple of the wavefront
-    hipLaunchKernelGGL((sa_x3_lean_kernel<C1, C2, C3, NS, NS % 64 == 0>), dim3((unsigned)blocks), dim3(256), 0, s, p,
-                       stride, q, idx, (int)n, (int)m, total, static_cast<const uint4 *>(packed), out, os, oo);
-    LAUNCH_CHECK();
-    return LIDAR_OK;
-}
-
-template <int C1, int C2, int C3, int NS, int L1, bool X1 = false>
+// LEAN (the shape table's flag, fp32 contract only): the wide feature levels run sa_x3_lean_kernel
+template <int C1, int C2, int C3, int NS, int L1, bool X1 = false, bool LEAN = false>
 int launch_x3(const float *p, int64_t stride, const float *q, const int32_t *idx, int64_t batch, int64_t n,
               int64_t m, const void *packed, float *out, int64_t os, int64_t oo, hipStream_t s,
               const float *xyz = nullptr, const float *centres = nullptr)
 {
-    constexpr int R = rows_for<NS, X1>();
-    const int64_t total = batch * m;
-    const int64_t blocks = (total + 3) / 4;
-    REQUIRE(blocks <= 0x7fffffff, "sa_group_mlp_x3: too many centres");
-    hipLaunchKernelGGL((sa_x3_kernel<C1, C2, C3, NS, L1, R, X1>), dim3((unsigned)blocks), dim3(256), 0, s, p, stride,
-                       q, idx, (int)n, (int)m, total, static_cast<const uint4 *>(packed), out, os, oo, xyz, centres,
-                       nullptr, 0.0f, 0.0f, nullptr);
+    static_assert(!LEAN || (L1 == L1_PRE && !X1), "the lean kernel: fp32-contract feature levels");
+    int64_t total, blocks;
+    if (int rc = lidar_sa::launch_geometry("sa_group_mlp_x3", batch, m, 4, total, blocks)) return rc;
+    if constexpr (LEAN) {
+        // a centre's row indices in one coalesced load whenever NS is a multiple of the wavefront
+        hipLaunchKernelGGL((sa_x3_lean_kernel<C1, C2, C3, NS, NS % 64 == 0>), dim3((unsigned)blocks), dim3(256), 0, s,
+                           p, stride, q, idx, (int)n, (int)m, total, static_cast<const uint4 *>(packed), out, os, oo);
+    } else {
+        hipLaunchKernelGGL((sa_x3_kernel<C1, C2, C3, NS, L1, rows_for<NS, X1>(), X1>), dim3((unsigned)blocks),
+                           dim3(256), 0, s, p, stride, q, idx, (int)n, (int)m, total,
+                           static_cast<const uint4 *>(packed), out, os, oo, xyz, centres, nullptr, 0.0f, 0.0f, nullptr);
+    }
     LAUNCH_CHECK();
     return LIDAR_OK;
 }
 
-template <int C1, int C2, int C3, int NS, bool X1>
-int launch_x3_bq(const float *xyz, const char *grid, const float *centres, int64_t batch, int64_t n, int64_t m,
-                 float radius, const void *packed, float *out, int64_t os, int64_t oo, int32_t *out_idx,
+// the fused ball query exists for the table's xyz entries only: XYZ false instantiates nothing
+template <int C1, int C2, int C3, int NS, bool XYZ>
+int launch_x3_bq(bool x1, const float *xyz, const char *grid, const float *centres, int64_t batch, int64_t n,
+                 int64_t m, float radius, const void *packed, float *out, int64_t os, int64_t oo, int32_t *out_idx,
                  hipStream_t s)
 {
-    constexpr int R = rows_for<NS, X1>();
-    const int64_t total = batch * m;
-    const int64_t blocks = (total + 3) / 4;
-    REQUIRE(blocks <= 0x7fffffff, "sa_group_mlp_bq: too many centres");
-    hipLaunchKernelGGL((sa_x3_kernel<C1, C2, C3, NS, L1_XYZ, R, X1, true>), dim3((unsigned)blocks), dim3(256), 0, s,
-                       xyz, (int64_t)3, centres, nullptr, (int)n, (int)m, total, static_cast<const uint4 *>(packed),
-                       out, os, oo, nullptr, nullptr, grid, radius, radius * radius, out_idx);
-    LAUNCH_CHECK();
-    return LIDAR_OK;
+    if constexpr (XYZ) {
+        int64_t total, blocks;
+        if (int rc = lidar_sa::launch_geometry("sa_group_mlp_bq", batch, m, 4, total, blocks)) return rc;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, xyz, (int64_t)3, centres, nullptr, (int)n,
+                               (int)m, total, static_cast<const uint4 *>(packed), out, os, oo, nullptr, nullptr, grid,
+                               radius, radius * radius, out_idx);
+        };
+        if (x1)
+            go(sa_x3_kernel<C1, C2, C3, NS, L1_XYZ, rows_for<NS, true>(), true, true>);
+        else
+            go(sa_x3_kernel<C1, C2, C3, NS, L1_XYZ, rows_for<NS, false>(), false, true>);
+        LAUNCH_CHECK();
+        return LIDAR_OK;
+    } else {
+        return lidar::fail(LIDAR_EINVAL, "lidar_sa_group_mlp_bq_f32: unsupported (widths, nsample) combination");
+    }
 }
 
 __host__ uint16_t bf16_rne(float f)
@@ -781,49 +768,31 @@ LIDAR_EXPORT int64_t lidar_mlp_packed_size_x3(int32_t xyz_level, int32_t c1, int
 
 // host packer: w1 (3 + ..., c1) read only for an xyz level (its xyz rows, fp32 as the 16-row
 // kernel's layer 1); w2 (c1, c2), w3 (c2, c3) scaled by their layer's power of two and split into
-// fp16 hi / lo in the fragment order (h3.hpp); the tail holds the exponents and layer 3's bound
+// fp16 hi / lo in the fragment order (h3.hpp; lidar_sa::write_fragments, shared with the X1 packer); the
+// tail holds the exponents and layer 3's bound
 LIDAR_EXPORT int lidar_mlp_pack_x3_f32(int32_t xyz_level, int32_t c1, int32_t c2, int32_t c3, const float *w1,
                                        const float *b1, const float *w2, const float *b2, const float *w3,
                                        const float *b3, void *packed)
 {
     REQUIRE(b1 && w2 && b2 && w3 && b3 && packed && (!xyz_level || w1), "lidar_mlp_pack_x3_f32: null pointer");
-    REQUIRE(c1 % 32 == 0 && c2 % 32 == 0 && c3 % 32 == 0 && c1 > 0 && c2 > 0 && c3 > 0,
-            "lidar_mlp_pack_x3_f32: widths must be positive multiples of 32");
-    char *o = static_cast<char *>(packed);
-    if (xyz_level) {
-        float *f = reinterpret_cast<float *>(o);
-        for (int t = 0; t < c1 / 16; ++t)
-            for (int l = 0; l < 64; ++l) {
-                const int qq = l >> 4;
-                *f++ = qq < 3 ? w1[(int64_t)qq * c1 + 16 * t + (l & 15)] : 0.0f;
-            }
-        o = reinterpret_cast<char *>(f);
-    }
+    if (int rc = lidar_sa::check_pack_widths("lidar_mlp_pack_x3_f32", c1, c2, c3)) return rc;
+    float *f = static_cast<float *>(packed);
+    if (xyz_level) f = lidar_sa::write_w1_lanes(f, w1, c1);
     X3Tail tail;
     tail.s2 = layer_exp(w2, (int64_t)c1 * c2);
     tail.s3 = layer_exp(w3, (int64_t)c2 * c3);
-    auto layer = [&](const float *w, int cin, int cout, int32_t sexp) {
-        const float sc = std::ldexp(1.0f, sexp);
-        uint16_t *u = reinterpret_cast<uint16_t *>(o);
-        for (int c = 0; c < cout / 32; ++c)
-            for (int s = 0; s < cin / 32; ++s)
-                for (int t = 0; t < 2; ++t)
-                    for (int h = 0; h < 2; ++h)
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j) {
-                                const int in = 32 * s + 16 * (j >> 2) + 4 * (l >> 4) + (j & 3);
-                                const float v = w[(int64_t)in * cout + 16 * (2 * c + t) + (l & 15)] * sc;
-                                const uint16_t hi = f16_bits(v);
-                                *u++ = h == 0 ? hi : f16_bits(v - f16_to_f(hi));
-                            }
-        o = reinterpret_cast<char *>(u);
+    // W 2^sexp split into fp16 hi (h = 0) and lo
+    auto h3 = [](int32_t sexp) {
+        return [sc = std::ldexp(1.0f, sexp)](float w, int h) {
+            const float v = w * sc;
+            const uint16_t hi = f16_bits(v);
+            return h == 0 ? hi : f16_bits(v - f16_to_f(hi));
+        };
     };
-    layer(w2, c1, c2, tail.s2);
-    layer(w3, c2, c3, tail.s3);
-    float *f = reinterpret_cast<float *>(o);
-    for (int i = 0; i < c1; ++i) *f++ = b1[i];
-    for (int i = 0; i < c2; ++i) *f++ = b2[i];
-    for (int i = 0; i < c3; ++i) *f++ = b3[i];
+    uint16_t *u = reinterpret_cast<uint16_t *>(f);
+    u = lidar_sa::write_fragments<2>(u, w2, c1, c2, h3(tail.s2));
+    u = lidar_sa::write_fragments<2>(u, w3, c2, c3, h3(tail.s3));
+    f = lidar_sa::write_biases(reinterpret_cast<float *>(u), b1, c1, b2, c2, b3, c3);
     // layer 3's input bound (lean kernel): max over channels of sum_k |W2[k][c]|, and max |b2|,
     // rounded up (float64 sums, then the next float up)
     double cs = 0.0, bm = 0.0;
@@ -846,31 +815,18 @@ LIDAR_EXPORT int lidar_sa_group_mlp_x3_f32(lidar_handle *h, int32_t xyz_level, c
                                            int32_t nsample, int32_t c1, int32_t c2, int32_t c3, const void *packed,
                                            float *out, int64_t out_stride, int64_t out_offset, void *stream)
 {
-    REQUIRE(h && p && q && idx && packed && out, "lidar_sa_group_mlp_x3_f32: null pointer");
-    REQUIRE(batch >= 0 && n >= 1 && m >= 1, "lidar_sa_group_mlp_x3_f32: bad sizes");
-    REQUIRE(xyz_level || (p_stride >= c1 && p_stride % 4 == 0), "lidar_sa_group_mlp_x3_f32: bad p_stride");
-    REQUIRE(out_offset >= 0 && out_offset + c3 <= out_stride,
-            "lidar_sa_group_mlp_x3_f32: output columns exceed out_stride");
+    if (int rc = lidar_sa::check_args("lidar_sa_group_mlp_x3_f32", h && p && q && idx && packed && out,
+                                      batch >= 0 && n >= 1 && m >= 1,
+                                      xyz_level || (p_stride >= c1 && p_stride % 4 == 0), out_offset, c3, out_stride))
+        return rc;
     if (batch == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // the wide feature levels (SA2, MSG's 128-sample branch) run the lean kernel
-    if (!xyz_level && c1 == 128 && c2 == 128 && c3 == 256) {
-        if (nsample == 64)
-            return launch_x3_lean<128, 128, 256, 64>(p, p_stride, q, idx, batch, n, m, packed, out, out_stride,
-                                                     out_offset, s);
-        if (nsample == 128)
-            return launch_x3_lean<128, 128, 256, 128>(p, p_stride, q, idx, batch, n, m, packed, out, out_stride,
-                                                      out_offset, s);
-    }
-#define LIDAR_SAX3(C1_, C2_, C3_, NS_, X_)                                                                   \
-    if (!!xyz_level == X_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                           \
-        return launch_x3<C1_, C2_, C3_, NS_, X_ ? L1_XYZ : L1_PRE>(p, p_stride, q, idx, batch, n, m, packed, out, \
-                                                                out_stride, out_offset, s);
-    LIDAR_SAX3(64, 64, 128, 32, true)
-    LIDAR_SAX3(32, 32, 64, 16, true)
-    LIDAR_SAX3(64, 96, 128, 128, true)
-    LIDAR_SAX3(64, 64, 128, 32, false)
+#define LIDAR_SAX3(C1_, C2_, C3_, NS_, X_, LEAN_)                                                              \
+    if (!!xyz_level == X_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                            \
+        return launch_x3<C1_, C2_, C3_, NS_, X_ ? L1_XYZ : L1_PRE, false, LEAN_>(p, p_stride, q, idx, batch, n, m, \
+                                                                                packed, out, out_stride, out_offset, s);
+    LIDAR_SA_SHAPES(LIDAR_SAX3)
 #undef LIDAR_SAX3
     return lidar::fail(LIDAR_EINVAL, "lidar_sa_group_mlp_x3_f32: unsupported (widths, nsample) combination");
 }
@@ -891,34 +847,14 @@ LIDAR_EXPORT int lidar_mlp_pack_x1_f32(int32_t c1, int32_t c2, int32_t c3, const
                                        void *packed)
 {
     REQUIRE(w1 && b1 && w2 && b2 && w3 && b3 && packed, "lidar_mlp_pack_x1_f32: null pointer");
-    REQUIRE(c1 % 32 == 0 && c2 % 32 == 0 && c3 % 32 == 0 && c1 > 0 && c2 > 0 && c3 > 0,
-            "lidar_mlp_pack_x1_f32: widths must be positive multiples of 32");
-    char *o = static_cast<char *>(packed);
-    float *f = reinterpret_cast<float *>(o);
-    for (int t = 0; t < c1 / 16; ++t)
-        for (int l = 0; l < 64; ++l) {
-            const int qq = l >> 4;
-            *f++ = qq < 3 ? bf16_to_f(bf16_rne(w1[(int64_t)qq * c1 + 16 * t + (l & 15)])) : 0.0f;
-        }
-    o = reinterpret_cast<char *>(f);
-    auto layer = [&](const float *w, int cin, int cout) {
-        uint16_t *u = reinterpret_cast<uint16_t *>(o);
-        for (int c = 0; c < cout / 32; ++c)
-            for (int s = 0; s < cin / 32; ++s)
-                for (int t = 0; t < 2; ++t)
-                    for (int l = 0; l < 64; ++l)
-                        for (int j = 0; j < 8; ++j) {
-                            const int in = 32 * s + 16 * (j >> 2) + 4 * (l >> 4) + (j & 3);
-                            *u++ = bf16_rne(w[(int64_t)in * cout + 16 * (2 * c + t) + (l & 15)]);
-                        }
-        o = reinterpret_cast<char *>(u);
-    };
-    layer(w2, c1, c2);
-    layer(w3, c2, c3);
-    f = reinterpret_cast<float *>(o);
-    for (int i = 0; i < c1; ++i) *f++ = b1[i];
-    for (int i = 0; i < c2; ++i) *f++ = b2[i];
-    for (int i = 0; i < c3; ++i) *f++ = b3[i];
+    if (int rc = lidar_sa::check_pack_widths("lidar_mlp_pack_x1_f32", c1, c2, c3)) return rc;
+    float *f = lidar_sa::write_w1_lanes(static_cast<float *>(packed), w1, c1,
+                                        [](float v) { return bf16_to_f(bf16_rne(v)); });
+    auto bf = [](float w, int) { return bf16_rne(w); };
+    uint16_t *u = reinterpret_cast<uint16_t *>(f);
+    u = lidar_sa::write_fragments<1>(u, w2, c1, c2, bf);
+    u = lidar_sa::write_fragments<1>(u, w3, c2, c3, bf);
+    lidar_sa::write_biases(reinterpret_cast<float *>(u), b1, c1, b2, c2, b3, c3);
     return LIDAR_OK;
 }
 
@@ -934,26 +870,22 @@ LIDAR_EXPORT int lidar_sa_group_mlp_x1_f32(lidar_handle *h, int32_t layer1_mode,
                                            int32_t c1, int32_t c2, int32_t c3, const void *packed, float *out,
                                            int64_t out_stride, int64_t out_offset, void *stream)
 {
-    REQUIRE(h && p && idx && packed && out, "lidar_sa_group_mlp_x1_f32: null pointer");
     REQUIRE(layer1_mode == 0 || layer1_mode == 2, "lidar_sa_group_mlp_x1_f32: layer1_mode must be 0 or 2");
     REQUIRE(layer1_mode == 2 ? (xyz && centres && p_stride >= c1 && p_stride % 4 == 0) : q != nullptr,
             "lidar_sa_group_mlp_x1_f32: mode 0 needs q = centres; mode 2 needs xyz, centres, p_stride >= c1");
-    REQUIRE(batch >= 0 && n >= 1 && m >= 1, "lidar_sa_group_mlp_x1_f32: bad sizes");
-    REQUIRE(out_offset >= 0 && out_offset + c3 <= out_stride,
-            "lidar_sa_group_mlp_x1_f32: output columns exceed out_stride");
+    if (int rc = lidar_sa::check_args("lidar_sa_group_mlp_x1_f32", h && p && idx && packed && out,
+                                      batch >= 0 && n >= 1 && m >= 1, true, out_offset, c3, out_stride))
+        return rc;
     if (batch == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define LIDAR_SAX1(C1_, C2_, C3_, NS_, M_)                                                                    \
-    if (layer1_mode == M_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                           \
-        return launch_x3<C1_, C2_, C3_, NS_, M_, true>(p, p_stride, M_ == 0 ? q : nullptr, idx, batch, n, m,   \
-                                                       packed, out, out_stride, out_offset, s, xyz, centres);
-    LIDAR_SAX1(32, 32, 64, 16, 0)
-    LIDAR_SAX1(64, 64, 128, 32, 0)
-    LIDAR_SAX1(64, 96, 128, 128, 0)
-    LIDAR_SAX1(64, 64, 128, 32, 2)
-    LIDAR_SAX1(128, 128, 256, 64, 2)
-    LIDAR_SAX1(128, 128, 256, 128, 2)
+    // the table's xyz entries are mode 0 (L1_XYZ), its feature entries mode 2 (L1_PX)
+#define LIDAR_SAX1(C1_, C2_, C3_, NS_, X_, LEAN_)                                                                 \
+    if (layer1_mode == (X_ ? 0 : 2) && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                     \
+        return launch_x3<C1_, C2_, C3_, NS_, X_ ? L1_XYZ : L1_PX, true>(p, p_stride, X_ ? q : nullptr, idx, batch, n, \
+                                                                       m, packed, out, out_stride, out_offset, s, \
+                                                                       xyz, centres);
+    LIDAR_SA_SHAPES(LIDAR_SAX1)
 #undef LIDAR_SAX1
     return lidar::fail(LIDAR_EINVAL, "lidar_sa_group_mlp_x1_f32: unsupported (widths, nsample) combination");
 }
@@ -969,25 +901,20 @@ LIDAR_EXPORT int lidar_sa_group_mlp_bq_f32(lidar_handle *h, int32_t x1, const fl
                                            float *out, int64_t out_stride, int64_t out_offset, int32_t *out_idx,
                                            void *stream)
 {
-    REQUIRE(h && xyz && grid && centres && packed && out, "lidar_sa_group_mlp_bq_f32: null pointer");
-    REQUIRE(batch >= 0 && n >= 1 && n < 0x3fffffff && m >= 1 && m < 0x7fffffff,
-            "lidar_sa_group_mlp_bq_f32: bad sizes");
     REQUIRE(radius >= 0.0f, "lidar_sa_group_mlp_bq_f32: negative radius");
-    REQUIRE(out_offset >= 0 && out_offset + c3 <= out_stride,
-            "lidar_sa_group_mlp_bq_f32: output columns exceed out_stride");
+    if (int rc = lidar_sa::check_args("lidar_sa_group_mlp_bq_f32", h && xyz && grid && centres && packed && out,
+                                      batch >= 0 && n >= 1 && n < 0x3fffffff && m >= 1 && m < 0x7fffffff, true,
+                                      out_offset, c3, out_stride))
+        return rc;
     if (batch == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const char *g = static_cast<const char *>(grid);
-#define LIDAR_SABQ(C1_, C2_, C3_, NS_)                                                                          \
-    if (c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                                                  \
-        return x1 ? launch_x3_bq<C1_, C2_, C3_, NS_, true>(xyz, g, centres, batch, n, m, radius, packed, out,    \
-                                                           out_stride, out_offset, out_idx, s)                   \
-                  : launch_x3_bq<C1_, C2_, C3_, NS_, false>(xyz, g, centres, batch, n, m, radius, packed, out,   \
-                                                            out_stride, out_offset, out_idx, s);
-    LIDAR_SABQ(64, 64, 128, 32)
-    LIDAR_SABQ(32, 32, 64, 16)
-    LIDAR_SABQ(64, 96, 128, 128)
+#define LIDAR_SABQ(C1_, C2_, C3_, NS_, X_, LEAN_)                                                              \
+    if (X_ && c1 == C1_ && c2 == C2_ && c3 == C3_ && nsample == NS_)                                           \
+        return launch_x3_bq<C1_, C2_, C3_, NS_, X_>(x1 != 0, xyz, g, centres, batch, n, m, radius, packed, out, \
+                                                    out_stride, out_offset, out_idx, s);
+    LIDAR_SA_SHAPES(LIDAR_SABQ)
 #undef LIDAR_SABQ
     return lidar::fail(LIDAR_EINVAL, "lidar_sa_group_mlp_bq_f32: unsupported (widths, nsample) combination");
 }

@@ -64,69 +64,94 @@ def resolve(cfg, n):
     return out
 
 
+# One codec for every weight tree here (the encoder's [level][branch][layer], the decoder's {"fp", "head"}):
+# a tree is lists of layers, a layer list is described by its [(cin, cout)], and these four do the work.
+def _draw_layers(rng, dims):
+    """[(W (cin, cout), b (cout,))] float32 for dims = [(cin, cout)]: conv1x1's default U(-1/sqrt(cin),
+    1/sqrt(cin)), W then b per layer (the order of draws is part of the seeds' meaning)."""
+    layers = []
+    for cin, cout in dims:
+        bound = 1.0 / np.sqrt(cin)
+        W = rng.uniform(-bound, bound, (cin, cout)).astype(np.float32)
+        b = rng.uniform(-bound, bound, cout).astype(np.float32)
+        layers.append((W, b))
+    return layers
+
+
+def _check_layers(what, dims, layers):
+    """layers = [(W, b)] against dims = [(cin, cout)] -> contiguous float32 arrays; ValueError, prefixed
+    `what`, on the first mismatch."""
+    if len(layers) != len(dims):
+        raise ValueError(f"{what}: {len(layers)} layers, expected {len(dims)}")
+    out = []
+    for j, ((cin, cout), (W, b)) in enumerate(zip(dims, layers)):
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        if W.shape != (cin, cout) or b.shape != (cout,):
+            raise ValueError(f"{what} layer {j}: W {W.shape}, b {b.shape}; expected ({cin}, {cout}) and ({cout},)")
+        out.append((W, b))
+    return out
+
+
+def _layer_arrays(prefix, layers):
+    """{<prefix>_<layer>_{W,b}: array}: a layer list as the flat entries of an .npz."""
+    return {f"{prefix}_{j}_{k}": a for j, wb in enumerate(layers) for k, a in zip("Wb", wb)}
+
+
+def _read_layers(z, prefix, n):
+    """The n layers _layer_arrays(prefix, ...) wrote into z."""
+    return [(z[f"{prefix}_{j}_W"], z[f"{prefix}_{j}_b"]) for j in range(n)]
+
+
+def _chain(cin, widths):
+    """[(cin, cout)] of consecutive layers of the given output widths."""
+    return list(zip([cin] + list(widths[:-1]), widths))
+
+
+def _sa_layer_dims(cfg):
+    """[level][branch] = [(cin, cout) per layer]: cin of a branch's first layer is 3 + the previous level's
+    channels."""
+    return [[_chain(3 + cin_feat, widths) for widths in lvl["mlps"]]
+            for lvl, cin_feat in zip(cfg["levels"], level_channels(cfg))]
+
+
 def init_weights(cfg, seed=0):
     """Deterministic random init (conv1x1 default: U(-1/sqrt(cin), 1/sqrt(cin)), BN folded
     at its fresh-init identity).  Returns [level][branch][layer] = (W (cin, cout), b)."""
     rng = np.random.default_rng(seed)
-    weights, cin_feat = [], 0
-    for lvl in cfg["levels"]:
-        branches, cout_total = [], 0
-        for widths in lvl["mlps"]:
-            layers, cin = [], 3 + cin_feat
-            for cout in widths:
-                bound = 1.0 / np.sqrt(cin)
-                W = rng.uniform(-bound, bound, (cin, cout)).astype(np.float32)
-                b = rng.uniform(-bound, bound, cout).astype(np.float32)
-                layers.append((W, b))
-                cin = cout
-            branches.append(layers)
-            cout_total += widths[-1]
-        weights.append(branches)
-        cin_feat = cout_total
-    return weights
+    return [[_draw_layers(rng, dims) for dims in lvl] for lvl in _sa_layer_dims(cfg)]
 
 
 def check_weights(cfg, weights):
     """Validate [level][branch][layer] = (W (cin, cout), b (cout,)) against cfg's widths (cin = 3 + the
     previous level's channels); returns them as contiguous float32 arrays.  Raises ValueError naming the
     first mismatch."""
-    out, cin_feat = [], 0
-    if len(weights) != len(cfg["levels"]):
-        raise ValueError(f"weights: {len(weights)} levels, the configuration has {len(cfg['levels'])}")
-    for li, (lvl, wl) in enumerate(zip(cfg["levels"], weights)):
-        if len(wl) != len(lvl["mlps"]):
-            raise ValueError(f"weights level {li}: {len(wl)} branches, the configuration has {len(lvl['mlps'])}")
-        branches = []
-        for bi, (widths, layers) in enumerate(zip(lvl["mlps"], wl)):
-            if len(layers) != len(widths):
-                raise ValueError(f"weights level {li} branch {bi}: {len(layers)} layers, expected {len(widths)}")
-            cin, conv = 3 + cin_feat, []
-            for j, (cout, (W, b)) in enumerate(zip(widths, layers)):
-                W = np.ascontiguousarray(W, dtype=np.float32)
-                b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
-                if W.shape != (cin, cout) or b.shape != (cout,):
-                    raise ValueError(f"weights level {li} branch {bi} layer {j}: W {W.shape}, b {b.shape}; "
-                                     f"expected ({cin}, {cout}) and ({cout},)")
-                conv.append((W, b))
-                cin = cout
-            branches.append(conv)
-        out.append(branches)
-        cin_feat = sum(w[-1] for w in lvl["mlps"])
+    dims = _sa_layer_dims(cfg)
+    if len(weights) != len(dims):
+        raise ValueError(f"weights: {len(weights)} levels, the configuration has {len(dims)}")
+    out = []
+    for li, (dl, wl) in enumerate(zip(dims, weights)):
+        if len(wl) != len(dl):
+            raise ValueError(f"weights level {li}: {len(wl)} branches, the configuration has {len(dl)}")
+        out.append([_check_layers(f"weights level {li} branch {bi}", d, layers)
+                    for bi, (d, layers) in enumerate(zip(dl, wl))])
     return out
 
 
 def save_weights(path, weights):
     """Weights to an .npz of plain arrays (keys l<level>_b<branch>_<layer>_{W,b}; no pickled objects)."""
-    arrs = {f"l{li}_b{bi}_{j}_{k}": a for li, wl in enumerate(weights) for bi, layers in enumerate(wl)
-            for j, wb in enumerate(layers) for k, a in zip("Wb", wb)}
+    arrs = {}
+    for li, wl in enumerate(weights):
+        for bi, layers in enumerate(wl):
+            arrs.update(_layer_arrays(f"l{li}_b{bi}", layers))
     np.savez(path, **arrs)
 
 
 def load_weights(path, cfg):
     """The .npz save_weights wrote, in cfg's layout (loaded with allow_pickle=False), validated."""
     with np.load(path, allow_pickle=False) as z:
-        w = [[[(z[f"l{li}_b{bi}_{j}_W"], z[f"l{li}_b{bi}_{j}_b"]) for j in range(len(widths))]
-              for bi, widths in enumerate(lvl["mlps"])] for li, lvl in enumerate(cfg["levels"])]
+        w = [[_read_layers(z, f"l{li}_b{bi}", len(widths)) for bi, widths in enumerate(lvl["mlps"])]
+             for li, lvl in enumerate(cfg["levels"])]
     return check_weights(cfg, w)
 
 
@@ -253,7 +278,8 @@ def ball_query_bin(radius, nsample, xyz, grid, slot=0):
     return grid
 
 
-# (xyz_level, c1, c2, c3, nsample) combinations lidar_sa_group_mlp16_f32 instantiates
+# (xyz_level, c1, c2, c3, nsample) of the fused kernels: csrc/sa_shapes.hpp's LIDAR_SA_SHAPES is the source (every
+# fused entry point expands it); repeated here because the library has no call that lists it
 MLP16_SHAPES = {(True, 64, 64, 128, 32), (True, 32, 32, 64, 16), (True, 64, 96, 128, 128), (False, 128, 128, 256, 64),
                 (False, 128, 128, 256, 128), (False, 64, 64, 128, 32)}
 
@@ -353,28 +379,29 @@ def layer1_points_x1(x_rows, xyz, cfeat, branches, cat=None):
     nat.call("lidar_concat_xyz_pad_f32", nat.handle(xyz.device.index), nat.ptr(xyz), B * N, nat.ptr(x_rows),
              x_rows.shape[1], cfeat, nat.stream_ptr())
     if cat is not None:
-        full = dense_x3s(x_rows, cat["w1f_x1"], cat["b1"], cat["w1f"].shape[1], relu=False, x1=True)
+        full = run_dense(x_rows, cat)
         return [full[:, o:o + w] for o, w in cat["cols"]]
-    return [dense_x3s(x_rows, br["pre_x1"]["w1f_x1"], br["pre_x1"]["b1"], br["pre_x1"]["w1f"].shape[1],
-                      relu=False, x1=True) for br in branches]
+    return [run_dense(x_rows, br["pre_x1"]) for br in branches]
 
 
 FUSE_LAYER1 = True  # backbones built while True fuse a bf16 level's per-point layer-1 GEMMs (A/B switch)
 
 
 def fused_layer1_x1(branches):
-    """The bf16-spec branches' per-point layer-1 weights side by side: {"w1f" (k, sum cp), "b1", "w1f_x1"
-    (the packed image), "cols": [(column offset, cp) per branch]} — None for fewer than two branches."""
+    """The bf16-spec branches' per-point layer-1 weights ("pre_x1") side by side: one dense_stack layer
+    (k, sum cp) plus "cols": [(column offset, cp) per branch] — None for fewer than two branches."""
     if len(branches) < 2 or any("pre_x1" not in br for br in branches):
         return None
-    ws = [br["pre_x1"]["w1f"] for br in branches]
+    ws = [br["pre_x1"]["w"] for br in branches]
     cols, o = [], 0
     for w in ws:
         cols.append((o, w.shape[1]))
         o += w.shape[1]
     w1f = torch.cat(ws, dim=1).contiguous()
-    b1 = torch.cat([br["pre_x1"]["b1"] for br in branches]).contiguous()
-    return {"w1f": w1f, "b1": b1, "w1f_x1": pack_dense_x3(w1f, x1=True), "cols": cols}
+    b1 = torch.cat([br["pre_x1"]["b"] for br in branches]).contiguous()
+    cat, = dense_stack([(w1f, b1)], "x1", [False], lambda a: a)
+    cat["cols"] = cols
+    return cat
 
 
 def group_mlp_x3(p, q, idx, n, packed, widths, out, out_offset=0, xyz_level=False):
@@ -444,28 +471,54 @@ def layer1_layout(w, b, cfeat, xyz_rows=True):
     return wp, bp
 
 
+def pad_chain(layers, kin):
+    """[(wp, bp)] of consecutive later layers: pad_layer, each layer's rows padded to the columns of what
+    feeds it (kin for the first)."""
+    out = []
+    for w, b in layers:
+        out.append(pad_layer(w, b, kin))
+        kin = out[-1][0].shape[1]
+    return out
+
+
 def mlp_layout(layers, cfeat):
     """[(wp, bp)] of a whole MLP: layer1_layout, then every later layer's rows padded to the columns
     of the one before it."""
-    out = [layer1_layout(*layers[0], cfeat)]
-    for w, b in layers[1:]:
-        out.append(pad_layer(w, b, out[-1][0].shape[1]))
+    first = layer1_layout(*layers[0], cfeat)
+    return [first] + pad_chain(layers[1:], first[0].shape[1])
+
+
+def dense_stack(padded, arith, relus, to_dev):
+    """The device operands of dense layers for run_dense: padded = [(wp (k, cp), bp (cp,))] in the padded
+    layout (pad_layer / layer1_layout: columns a multiple of 128), arith "x3" (h3 GEMM), "x1" (the bf16
+    spec's) or "f32" (the native fp32 GEMM), relus one flag per layer.  -> [{"w", "b", "cout" (= cp), "relu",
+    "arith" and, unless f32, "packed": pack_dense_x3's image}].  Moved to the device kind by kind: every w,
+    every b, then the images."""
+    ws = [to_dev(wp) for wp, _ in padded]
+    bs = [to_dev(bp) for _, bp in padded]
+    out = [{"w": w, "b": b, "cout": w.shape[1], "relu": bool(relu), "arith": arith}
+           for w, b, relu in zip(ws, bs, relus)]
+    if arith != "f32":
+        for lay in out:
+            lay["packed"] = pack_dense_x3(lay["w"], x1=arith == "x1")
     return out
+
+
+def run_dense(a, layer, slot=0, out=None, pool_rows=0):
+    """a (rows, k) through one dense_stack layer: a W + b [ReLU] [max over runs of pool_rows rows], on the
+    GEMM of the layer's arithmetic — the one place that chooses between dense and dense_x3s."""
+    if layer["arith"] == "f32":
+        return dense(a, layer["w"], layer["b"], relu=layer["relu"], pool_rows=pool_rows, out=out)
+    return dense_x3s(a, layer["packed"], layer["b"], layer["cout"], relu=layer["relu"], pool_rows=pool_rows,
+                     out=out, x1=layer["arith"] == "x1", slot=slot)
 
 
 def generic_branch_weights(layers, cfeat, to_dev, arith):
-    """Dense-GEMM operands of an SA branch of any shape (sa_branch_generic), in mlp_layout: layer 1's
-    rows in the grouped rows' order [f..., x, y, z, 0-pad], every layer's columns (and the next layer's
-    rows) zero-padded to a multiple of 128.  arith: "x3" (h3 images), "x1" (bf16-spec images) or "f32"
-    (the native fp32 GEMM's plain weights)."""
-    out = {"k": _kpad(cfeat), "layers": [], "c3": layers[-1][0].shape[1], "arith": arith}
-    for wp, bp in mlp_layout(layers, cfeat):
-        wd = to_dev(wp)
-        lay = {"w": wd, "b": to_dev(bp), "cout": wp.shape[1]}
-        if arith != "f32":
-            lay["packed"] = pack_dense_x3(wd, x1=arith == "x1")
-        out["layers"].append(lay)
-    return out
+    """Dense-GEMM operands of an SA branch of any shape (sa_branch_generic): the dense_stack of mlp_layout
+    (layer 1's rows in the grouped rows' order [f..., x, y, z, 0-pad], every layer's columns and the next
+    layer's rows zero-padded to a multiple of 128), ReLU after every layer.  arith as dense_stack's."""
+    return {"k": _kpad(cfeat), "c3": layers[-1][0].shape[1], "arith": arith,
+            "layers": dense_stack(mlp_layout(layers, cfeat), arith, [True] * len(layers), to_dev)}
 
 
 def sa_branch_generic(feat, cfeat, xyz, centres, idx, gw, out, out_offset=0, max_bytes=1 << 30, slot=0):
@@ -505,24 +558,22 @@ def sa_branch_generic(feat, cfeat, xyz, centres, idx, gw, out, out_offset=0, max
                  nat.ptr(rows), R, kp, nat.stream_ptr())
         a = rows
         for lay in gw["layers"]:
-            if gw["arith"] == "f32":
-                a = dense(a, lay["w"], lay["b"], relu=True)
-            else:
-                a = dense_x3s(a, lay["packed"], lay["b"], lay["cout"], relu=True, x1=gw["arith"] == "x1", slot=slot)
+            a = run_dense(a, lay, slot=slot)
         dst = out[b0:b0 + nb]
         nat.call("lidar_group_max_f32", h, nat.ptr(a), a.shape[1], nb * M, ns, gw["c3"], nat.ptr(dst),
                  out.shape[2], out_offset, nat.stream_ptr())
     return out
 
 
-def layer1_weights(layer, cfeat, to_dev):
-    """(W1 (3 + cfeat, c1), b1) -> the per-point GEMM operands of layer1_per_point:
-    w1 rows [f..., x, y, z, 0-pad] (k padded to 16), wq rows [x, y, z, 0-pad] (16), columns
-    zero-padded to a multiple of 128 (the dense kernel's tile)."""
+def layer1_weights(layer, cfeat, to_dev, arith="f32"):
+    """(W1 (3 + cfeat, c1), b1) -> the per-point GEMM operands of layer1_per_point, two dense_stack layers
+    without ReLU: "w1" rows [f..., x, y, z, 0-pad] (k padded to 16) with b1, "wq" rows [x, y, z, 0-pad] (16)
+    with a zero bias; columns zero-padded to a multiple of 128 (the dense kernel's tile)."""
     w1, b1 = layer
     w1p, bp = layer1_layout(w1, b1, cfeat)
     wq, _ = pad_layer(w1[:3], b1, 16)
-    return {"w1": to_dev(w1p), "b1": to_dev(bp), "wq": to_dev(wq), "zero": to_dev(np.zeros_like(bp))}
+    return {"w1": dense_stack([(w1p, bp)], arith, [False], to_dev)[0],
+            "wq": dense_stack([(wq, np.zeros_like(bp))], arith, [False], to_dev)[0]}
 
 
 def centre_layer1(new_xyz, branches, out=None, slot=0):
@@ -535,12 +586,10 @@ def centre_layer1(new_xyz, branches, out=None, slot=0):
     rq = (B * M + 127) // 128 * 128
     res = []
     for i, br in enumerate(branches):
-        pre = br["pre"]
-        cp = pre["w1"].shape[1]
         cpad, q = out[i] if out is not None else (torch.zeros((rq, 16), dtype=torch.float32, device=dev), None)
         cpad, q = cpad[:rq], (q[:rq] if q is not None else None)
         nat.call("lidar_concat_xyz_pad_f32", h, nat.ptr(new_xyz), B * M, nat.ptr(cpad), 16, 0, nat.stream_ptr())
-        res.append(dense_x3s(cpad, pre["wq_x3"], pre["zero"], cp, relu=False, out=q, slot=slot))
+        res.append(run_dense(cpad, br["pre"]["wq"], slot=slot, out=q))
     return res
 
 
@@ -551,8 +600,8 @@ def layer1_per_point(x_rows, xyz, cfeat, new_xyz, branches, x3=True):
     (R = B*N rounded up to 128; the previous level wrote f in place), xyz (B, N, 3);
     new_xyz (B, M, 3).  Returns per branch (P, Q): P = x_rows W1' + b1 (R, c1),
     Q = [c, 0] W1_xyz' (B*M rounded to 128, c1), both without ReLU (columns padded to a
-    multiple of 128 with zero weights).  x3: on the h3 GEMM (fp32 rows in, scaled and split in the
-    tile loop); else the native fp32 MFMA GEMM."""
+    multiple of 128 with zero weights), each on the GEMM of its layer1_weights arithmetic.  x3: the
+    launch order of the h3 path (every Q by centre_layer1, then every P); else P, Q branch by branch."""
     B, N, _ = xyz.shape
     M = new_xyz.shape[1]
     R, kp = x_rows.shape
@@ -561,13 +610,11 @@ def layer1_per_point(x_rows, xyz, cfeat, new_xyz, branches, x3=True):
     nat.call("lidar_concat_xyz_pad_f32", h, nat.ptr(xyz), B * N, nat.ptr(x_rows), kp, cfeat, nat.stream_ptr())
     if x3:
         qs = centre_layer1(new_xyz, branches)
-        return [(dense_x3s(x_rows, br["pre"]["w1_x3"], br["pre"]["b1"], br["pre"]["w1"].shape[1], relu=False), q)
-                for br, q in zip(branches, qs)]
+        return [(run_dense(x_rows, br["pre"]["w1"]), q) for br, q in zip(branches, qs)]
     rq = (B * M + 127) // 128 * 128
     cpad = torch.zeros((rq, 16), dtype=torch.float32, device=dev)
     nat.call("lidar_concat_xyz_pad_f32", h, nat.ptr(new_xyz), B * M, nat.ptr(cpad), 16, 0, nat.stream_ptr())
-    return [(dense(x_rows, br["pre"]["w1"], br["pre"]["b1"], relu=False),
-             dense(cpad, br["pre"]["wq"], br["pre"]["zero"], relu=False)) for br in branches]
+    return [(run_dense(x_rows, br["pre"]["w1"]), run_dense(cpad, br["pre"]["wq"])) for br in branches]
 
 
 def pack_dense_x3(w, x1=False):
@@ -806,16 +853,8 @@ def _fp_layer_dims(cfg, fp_cfg, num_classes):
         raise ValueError("num_classes must be at least 1")
     dims = []
     for i, ((c2, c1), widths) in enumerate(zip(fp_input_widths(cfg, fp_cfg), fp_cfg["mlps"])):
-        cin, lay = c2 + c1, []
-        for cout in widths:
-            lay.append((cin, cout))
-            cin = cout
-        dims.append((f"fp{i}", lay))
-    lay = []
-    for cout in list(fp_cfg["head"]) + [num_classes]:
-        lay.append((cin, cout))
-        cin = cout
-    dims.append(("head", lay))
+        dims.append((f"fp{i}", _chain(c2 + c1, widths)))
+    dims.append(("head", _chain(dims[-1][1][-1][1], list(fp_cfg["head"]) + [num_classes])))
     return dims
 
 
@@ -824,18 +863,8 @@ def init_fp_weights(cfg, fp_cfg=FP_SSG, num_classes=2, seed=0):
     its identity).  Returns {"fp": [level][layer] = (W (cin, cout), b), "head": [layer] = (W, b)}: an FP
     level's rows are [interpolated (c2), skip (c1)]; the head's last layer is the classifier (no ReLU)."""
     rng = np.random.default_rng(seed)
-    out = {"fp": [], "head": []}
-    for name, lay in _fp_layer_dims(cfg, fp_cfg, num_classes):
-        layers = []
-        for cin, cout in lay:
-            bound = 1.0 / np.sqrt(cin)
-            layers.append((rng.uniform(-bound, bound, (cin, cout)).astype(np.float32),
-                           rng.uniform(-bound, bound, cout).astype(np.float32)))
-        if name == "head":
-            out["head"] = layers
-        else:
-            out["fp"].append(layers)
-    return out
+    trees = [_draw_layers(rng, lay) for _, lay in _fp_layer_dims(cfg, fp_cfg, num_classes)]
+    return {"fp": trees[:-1], "head": trees[-1]}
 
 
 def check_fp_weights(cfg, fp_cfg, num_classes, fp_weights):
@@ -847,39 +876,24 @@ def check_fp_weights(cfg, fp_cfg, num_classes, fp_weights):
         raise ValueError("fp_weights must be a dict with the keys 'fp' and 'head'")
     if len(fp_weights["fp"]) != len(dims) - 1:
         raise ValueError(f"fp_weights: {len(fp_weights['fp'])} FP levels, the configuration has {len(dims) - 1}")
-    out = {"fp": [], "head": []}
-    for (name, lay), layers in zip(dims, list(fp_weights["fp"]) + [fp_weights["head"]]):
-        if len(layers) != len(lay):
-            raise ValueError(f"fp_weights {name}: {len(layers)} layers, expected {len(lay)}")
-        conv = []
-        for j, ((cin, cout), (W, b)) in enumerate(zip(lay, layers)):
-            W = np.ascontiguousarray(W, dtype=np.float32)
-            b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
-            if W.shape != (cin, cout) or b.shape != (cout,):
-                raise ValueError(f"fp_weights {name} layer {j}: W {W.shape}, b {b.shape}; "
-                                 f"expected ({cin}, {cout}) and ({cout},)")
-            conv.append((W, b))
-        if name == "head":
-            out["head"] = conv
-        else:
-            out["fp"].append(conv)
-    return out
+    trees = [_check_layers(f"fp_weights {name}", lay, layers)
+             for (name, lay), layers in zip(dims, list(fp_weights["fp"]) + [fp_weights["head"]])]
+    return {"fp": trees[:-1], "head": trees[-1]}
 
 
 def save_fp_weights(path, fp_weights):
     """Decoder weights to an .npz of plain arrays (keys fp<level>_<layer>_{W,b}, head_<layer>_{W,b})."""
-    arrs = {f"fp{i}_{j}_{k}": a for i, layers in enumerate(fp_weights["fp"]) for j, wb in enumerate(layers)
-            for k, a in zip("Wb", wb)}
-    arrs.update({f"head_{j}_{k}": a for j, wb in enumerate(fp_weights["head"]) for k, a in zip("Wb", wb)})
+    arrs = _layer_arrays("head", fp_weights["head"])
+    for i, layers in enumerate(fp_weights["fp"]):
+        arrs.update(_layer_arrays(f"fp{i}", layers))
     np.savez(path, **arrs)
 
 
 def load_fp_weights(path, cfg, fp_cfg=FP_SSG, num_classes=2):
     """The .npz save_fp_weights wrote (loaded with allow_pickle=False), validated by check_fp_weights."""
     with np.load(path, allow_pickle=False) as z:
-        w = {"fp": [[(z[f"fp{i}_{j}_W"], z[f"fp{i}_{j}_b"]) for j in range(len(widths))]
-                    for i, widths in enumerate(fp_cfg["mlps"])],
-             "head": [(z[f"head_{j}_W"], z[f"head_{j}_b"]) for j in range(len(fp_cfg["head"]) + 1)]}
+        w = {"fp": [_read_layers(z, f"fp{i}", len(widths)) for i, widths in enumerate(fp_cfg["mlps"])],
+             "head": _read_layers(z, "head", len(fp_cfg["head"]) + 1)}
     return check_fp_weights(cfg, fp_cfg, num_classes, w)
 
 
@@ -968,13 +982,12 @@ class PointNet2Backbone:
         self.timers = None  # set to a _Timers() to time every launch
 
     def _build_group_all(self, layers, cfeat, t):
-        """The group_all level's entry: its MLP in mlp_layout (the dense GEMMs' operands) and, for the
-        h3 chain, the packed x3 B fragments and each layer's exponent bounds."""
+        """The group_all level's entry: "layers", the dense_stack of its MLP in mlp_layout, and, for the
+        h3 chain, each layer's exponent bounds."""
         lay = mlp_layout(layers, cfeat)
         entry = {"group_all": True, "k": _kpad(cfeat), "cfeat": cfeat, "cout": layers[-1][0].shape[1],
-                 "w": [t(w) for w, _ in lay], "b": [t(b) for _, b in lay]}
-        if self.x3:  # packed once into x3 B fragments
-            entry["w_x3"] = [pack_dense_x3(w) for w in entry["w"]]
+                 "layers": dense_stack(lay, "x3" if self.x3 else "f32", [True] * len(lay), t)}
+        if self.x3:
             entry["h3_bounds"] = [h3_bounds(w, b) for w, b in lay]
         return entry
 
@@ -993,14 +1006,9 @@ class PointNet2Backbone:
         key, pk = _IMAGE[arith]
         br[key] = torch.from_numpy(_pack_branch(pk, layers, xyz_level)).to(self.device)
         if not xyz_level and arith == "x1":  # W1_f: rows [f..., (x, y, z) = 0, 0-pad], columns to 128
-            w1f, b1 = layer1_layout(*layers[0], cfeat, xyz_rows=False)
-            br["pre_x1"] = {"w1f": t(w1f), "b1": t(b1)}
-            br["pre_x1"]["w1f_x1"] = pack_dense_x3(br["pre_x1"]["w1f"], x1=True)
+            br["pre_x1"], = dense_stack([layer1_layout(*layers[0], cfeat, xyz_rows=False)], "x1", [False], t)
         elif not xyz_level:
-            br["pre"] = layer1_weights(layers[0], cfeat, t)
-            if arith == "x3":
-                br["pre"]["w1_x3"] = pack_dense_x3(br["pre"]["w1"])
-                br["pre"]["wq_x3"] = pack_dense_x3(br["pre"]["wq"])
+            br["pre"] = layer1_weights(layers[0], cfeat, t, arith)
         return br
 
     def _grid_buffer(self, B, N, device):
@@ -1132,16 +1140,16 @@ class PointNet2Backbone:
             x2 = x.view(B, M, kp)[:, sel].reshape(B * mp, kp).contiguous()
             M, rows = mp, B * mp
         t = self.timers
-        ws, bs = lvl["w"], lvl["b"]
+        l1, l2, l3 = lvl["layers"]
         if self.x3:  # h3 planes between the layers (split once, by the producer); dense3 fuses the max-pool
-            wp, bd = lvl["w_x3"], lvl["h3_bounds"]
-            h1, e1 = _call(t, "sa3_dense1", B, dense_h3p, x2, None, wp[0], bs[0], ws[0].shape[1], 1, bd[0])
-            h2, e2 = _call(t, "sa3_dense2", B, dense_h3p, h1, e1, wp[1], bs[1], ws[1].shape[1], 1, bd[1])
-            return _call(t, "sa3_dense3_pool", B, dense_h3p, h2, e2, wp[2], bs[2], ws[2].shape[1], 2, pool_rows=M)
-        h1 = _call(t, "sa3_dense1", B, dense_relu, x2, ws[0], bs[0])
-        h2 = _call(t, "sa3_dense2", B, dense_relu, h1, ws[1], bs[1])
-        out = torch.zeros((rows // M, ws[2].shape[1]), dtype=torch.float32, device=x.device)
-        return _call(t, "sa3_dense3_pool", B, dense_relu, h2, ws[2], bs[2], pool_rows=M, out=out)
+            bd = lvl["h3_bounds"]
+            h1, e1 = _call(t, "sa3_dense1", B, dense_h3p, x2, None, l1["packed"], l1["b"], l1["cout"], 1, bd[0])
+            h2, e2 = _call(t, "sa3_dense2", B, dense_h3p, h1, e1, l2["packed"], l2["b"], l2["cout"], 1, bd[1])
+            return _call(t, "sa3_dense3_pool", B, dense_h3p, h2, e2, l3["packed"], l3["b"], l3["cout"], 2, pool_rows=M)
+        h1 = _call(t, "sa3_dense1", B, run_dense, x2, l1)
+        h2 = _call(t, "sa3_dense2", B, run_dense, h1, l2)
+        out = torch.zeros((rows // M, l3["cout"]), dtype=torch.float32, device=x.device)
+        return _call(t, "sa3_dense3_pool", B, run_dense, h2, l3, pool_rows=M, out=out)
 
     __call__ = forward
 
@@ -1166,32 +1174,15 @@ class PointNet2Segmenter:
                            else init_fp_weights(cfg, fp_cfg, num_classes, seed))
         self.fp = []
         cp = 0
+        arith, t = "x3" if self.x3 else "f32", lambda a: torch.from_numpy(a).to(self.device)
         for (c2, c1), layers in zip(fp_input_widths(cfg, fp_cfg), self.fp_weights["fp"]):
             ldo = (c2 + c1 + 15) // 16 * 16  # the interpolated rows' stride: k of the level's first GEMM
-            lay = self._layers(layers, ldo, [True] * len(layers))
+            lay = dense_stack(pad_chain(layers, ldo), arith, [True] * len(layers), t)
             self.fp.append({"c2": c2, "c1": c1, "ldo": ldo, "layers": lay, "cout": layers[-1][0].shape[1]})
             cp = lay[-1]["cout"]
         head = self.fp_weights["head"]
-        self.head = self._layers(head, cp, [True] * (len(head) - 1) + [False])  # the classifier: no ReLU
-
-    def _layers(self, layers, kin, relus):
-        """Device operands of consecutive dense layers in pad_layer's layout (rows padded to the width of
-        what feeds them, columns to a multiple of 128), packed once for the h3 GEMM."""
-        out = []
-        for (w, b), relu in zip(layers, relus):
-            wp, bp = pad_layer(w, b, kin)
-            wd = torch.from_numpy(wp).to(self.device)
-            lay = {"w": wd, "b": torch.from_numpy(bp).to(self.device), "cout": wp.shape[1], "relu": relu}
-            if self.x3:
-                lay["packed"] = pack_dense_x3(wd)
-            out.append(lay)
-            kin = wp.shape[1]
-        return out
-
-    def _dense(self, a, lay):
-        if self.x3:
-            return dense_x3s(a, lay["packed"], lay["b"], lay["cout"], relu=lay["relu"])
-        return dense(a, lay["w"], lay["b"], relu=lay["relu"])
+        # the classifier: no ReLU
+        self.head = dense_stack(pad_chain(head, cp), arith, [True] * (len(head) - 1) + [False], t)
 
     def point_sets(self, xyz, levels, global_feat):
         """[(xyz, features or None)] of P_0 (the frame) .. P_L from forward(keep_levels=True)'s output: a
@@ -1270,7 +1261,7 @@ class PointNet2Segmenter:
             _call(t, f"fp{i}_interpolate", nb, three_interpolate, kfeat, idx, w, skip if c1 else None, rows)
             a = rows
             for j, lay in enumerate(fp["layers"]):
-                a = _call(t, f"fp{i}_dense{j + 1}", nb, self._dense, a, lay)
+                a = _call(t, f"fp{i}_dense{j + 1}", nb, run_dense, a, lay)
             feats = a[:nb * n].view(nb, n, a.shape[1])[..., :fp["cout"]]
             if keep:
                 kept["fp"].append({"rows": rows[:nb * n].view(nb, n, fp["ldo"])[..., :c2 + c1], "idx": idx, "weight": w,
@@ -1280,7 +1271,7 @@ class PointNet2Segmenter:
         for j, lay in enumerate(self.head):
             if keep and j == len(self.head) - 1:
                 kept["head"] = a[:nb * n].view(nb, n, a.shape[1])[..., :self.fp_weights["head"][-1][0].shape[0]]
-            a = _call(t, f"head_dense{j + 1}", nb, self._dense, a, lay)
+            a = _call(t, f"head_dense{j + 1}", nb, run_dense, a, lay)
         return a, kept
 
     def forward(self, xyz, max_bytes=1 << 30):

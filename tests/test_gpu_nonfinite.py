@@ -392,15 +392,11 @@ def run_feat_kernel(path, dev, case, layers, f, off=3):
     rows[:SA_N, :cfeat] = t(f[0])
     out = torch.full((1, SA_M, widths[-1] + 5), SENT, dtype=torch.float32, device=dev)
     if l1 == "x1":
-        w1f, b1 = pn.layer1_layout(*layers[0], cfeat, xyz_rows=False)
-        pre = {"w1f": t(w1f), "b1": t(b1)}
-        pre["w1f_x1"] = pn.pack_dense_x3(pre["w1f"], x1=True)
+        pre, = pn.dense_stack([pn.layer1_layout(*layers[0], cfeat, xyz_rows=False)], "x1", [False], t)
         P, = pn.layer1_points_x1(rows, x, cfeat, [{"pre_x1": pre}])
         pn.group_mlp_x1(P, gi, SA_N, t(pn.pack_branch_x1(layers)), widths, out, off, xyz=x, centres=c)
     else:
-        pre = pn.layer1_weights(layers[0], cfeat, t)
-        if l1 == "h3":
-            pre["w1_x3"], pre["wq_x3"] = pn.pack_dense_x3(pre["w1"]), pn.pack_dense_x3(pre["wq"])
+        pre = pn.layer1_weights(layers[0], cfeat, t, "x3" if l1 == "h3" else "f32")
         (P, Q), = pn.layer1_per_point(rows, x, cfeat, c, [{"pre": pre}], x3=l1 == "h3")
         if kernel == "mlp16":
             pn.group_mlp16(P, Q, gi, SA_N, t(pn.pack_branch16(layers, False)), widths, out, off)

@@ -1072,23 +1072,23 @@ def test_backbone_weight_layouts(cuda, cfg_name, dtype):
     the group_all entry's three layers and, in the bf16 spec, every feature-level branch's W1_f (xyz rows zero)."""
     bb = pn.PointNet2Backbone(pn.CONFIGS[cfg_name], device=cuda, seed=11, dtype=dtype)
     ga = bb.levels[-1]
-    assert ga.get("group_all") and len(ga["w"]) == len(ga["b"]) == 3
+    assert ga.get("group_all") and len(ga["layers"]) == 3
     kin = None
     for j, (w, b) in enumerate(bb.weights[-1][0]):
         ww, wb = _physical_rows(w, b, ga["cfeat"], kin)
-        assert np.array_equal(ga["w"][j].cpu().numpy(), ww), j
-        assert np.array_equal(ga["b"][j].cpu().numpy(), wb), j
+        assert np.array_equal(ga["layers"][j]["w"].cpu().numpy(), ww), j
+        assert np.array_equal(ga["layers"][j]["b"].cpu().numpy(), wb), j
         kin = ww.shape[1]
-    assert ga["w"][0].shape[0] == ga["k"]
+    assert ga["layers"][0]["w"].shape[0] == ga["k"]
     if dtype == "bf16":
         lvl = bb.levels[1]
         assert len(lvl["branches"]) == 3
         for br, layers in zip(lvl["branches"], bb.weights[1]):
             ww, wb = _physical_rows(*layers[0], lvl["cfeat"], xyz_rows=False)
-            got = br["pre_x1"]["w1f"].cpu().numpy()
+            got = br["pre_x1"]["w"].cpu().numpy()
             assert np.array_equal(got, ww) and got.shape[0] == lvl["k"]
             assert not got[lvl["cfeat"]:].any()  # the xyz rows (and the padding) are zero
-            assert np.array_equal(br["pre_x1"]["b1"].cpu().numpy(), wb)
+            assert np.array_equal(br["pre_x1"]["b"].cpu().numpy(), wb)
 
 
 def test_streaming_host_feed_rejected_batch_drops_nothing(cuda):

@@ -1,4 +1,4 @@
-"""The one weight layout of pointnet2 (layer1_weights, generic_branch_weights), against arrays built here
+"""The one weight layout of pointnet2 (layer1_weights, generic_branch_weights: dense_stack layers), against arrays built here
 from the rule their docstrings state: canonical rows [x, y, z, f...] become [f..., x, y, z, 0-pad] with k
 padded to 16, columns (and the next layer's rows) zero-padded to a multiple of 128.  No GPU, no library."""
 import numpy as np
@@ -32,13 +32,16 @@ def _check_layer1_weights(cfeat, c1):
     w = rng.standard_normal((3 + cfeat, c1)).astype(np.float32)
     b = rng.standard_normal(c1).astype(np.float32)
     got = pn.layer1_weights((w, b), cfeat, same)
-    assert sorted(got) == ["b1", "w1", "wq", "zero"]
-    assert all(v.dtype == np.float32 for v in got.values())
-    assert got["w1"].shape == (KP[cfeat], CP[c1])
-    assert np.array_equal(got["w1"], _want_layer1(w, cfeat))
-    assert np.array_equal(got["wq"], np.pad(w[:3], ((0, 13), (0, CP[c1] - c1))))  # the xyz rows over 16
-    assert np.array_equal(got["b1"], np.pad(b, (0, CP[c1] - c1)))
-    assert np.array_equal(got["zero"], np.zeros(CP[c1], np.float32))
+    assert sorted(got) == ["w1", "wq"]
+    for lay in got.values():  # fp32 dense_stack layers without ReLU: plain weights, no packed image
+        assert sorted(lay) == ["arith", "b", "cout", "relu", "w"]
+        assert lay["arith"] == "f32" and lay["relu"] is False and lay["cout"] == CP[c1]
+        assert lay["w"].dtype == lay["b"].dtype == np.float32
+    assert got["w1"]["w"].shape == (KP[cfeat], CP[c1])
+    assert np.array_equal(got["w1"]["w"], _want_layer1(w, cfeat))
+    assert np.array_equal(got["wq"]["w"], np.pad(w[:3], ((0, 13), (0, CP[c1] - c1))))  # the xyz rows over 16
+    assert np.array_equal(got["w1"]["b"], np.pad(b, (0, CP[c1] - c1)))
+    assert np.array_equal(got["wq"]["b"], np.zeros(CP[c1], np.float32))
 
 
 @pytest.mark.parametrize("cfeat", sorted(KP))
@@ -52,7 +55,8 @@ def test_weight_layout(cfeat):
     kin = KP[cfeat]
     for j, ((w, b), lay) in enumerate(zip(layers, got["layers"])):
         c = w.shape[1]
-        assert sorted(lay) == ["b", "cout", "w"]  # fp32: plain weights, no packed image
+        assert sorted(lay) == ["arith", "b", "cout", "relu", "w"]  # fp32: plain weights, no packed image
+        assert lay["arith"] == "f32" and lay["relu"] is True
         assert lay["cout"] == CP[c] and lay["w"].shape == (kin, CP[c]) and lay["w"].dtype == np.float32
         # layer j + 1's rows are padded to layer j's cp
         want = _want_layer1(w, cfeat) if j == 0 else np.pad(w, ((0, kin - w.shape[0]), (0, CP[c] - c)))
@@ -61,4 +65,5 @@ def test_weight_layout(cfeat):
         kin = CP[c]
     # the two functions agree on layer 1
     pre = pn.layer1_weights(layers[0], cfeat, same)
-    assert np.array_equal(pre["w1"], got["layers"][0]["w"]) and np.array_equal(pre["b1"], got["layers"][0]["b"])
+    assert np.array_equal(pre["w1"]["w"], got["layers"][0]["w"])
+    assert np.array_equal(pre["w1"]["b"], got["layers"][0]["b"])
