@@ -340,16 +340,36 @@ int lidar_histogram2d_f64(lidar_handle *h, const double *a, const double *b, int
 int lidar_parse_ascii_xyz(const char *buf, int64_t len, int64_t first, int64_t max_lines, double *out,
                           int64_t cap, int64_t *n_out);
 
+/* The scalars block of a preprocessed frame: LIDAR_SCALARS doubles, the public slots below (the
+ * others are the library's own).  The Python host layer restates them in density_abi.py. */
+enum {
+    LIDAR_S_N_IN = 0,           /* inliers of the 3-sigma filter */
+    LIDAR_S_N_GROUND = 1,
+    LIDAR_S_N_NONGROUND = 2,
+    LIDAR_S_Z_THRESHOLD = 3,    /* the 30th-percentile ground split */
+    LIDAR_S_EPS = 4,            /* DBSCAN's eps */
+    LIDAR_S_DIMS = 5,           /* 5..10: x_min, x_max, y_min, y_max, z_min, z_max */
+    LIDAR_S_PLANE = 11,         /* 11..14: ground plane a, b, c, d */
+    LIDAR_S_STATUS = 15,        /* LIDAR_STATUS_* */
+    LIDAR_S_MEAN = 16,          /* 16..18: 3-sigma mean */
+    LIDAR_S_STD = 19,           /* 19..21: 3-sigma std */
+    LIDAR_S_SCALER_MEAN = 22,   /* 22..24: StandardScaler mean */
+    LIDAR_S_SCALER_SCALE = 25,  /* 25..27: StandardScaler scale */
+    LIDAR_S_SCALED_BBOX = 28,   /* 28..33: lo (3), hi (3) of the scaled non-ground points */
+    LIDAR_S_N_CLUSTERS = 39,
+    LIDAR_S_PLANE_KIND = 40,    /* 0 lstsq, 1 min-z fallback, 2 rank-deficient ground */
+    LIDAR_SCALARS = 64,
+    LIDAR_STATUS_OK = 0,
+    LIDAR_STATUS_NO_INLIER = 1, /* no point survives the 3-sigma filter -> the reference's IndexError */
+    LIDAR_STATUS_EMPTY = 2      /* a batch frame without points -> the reference's ValueError */
+};
+
 /* Whole preprocess_lidar_data (utils/data_processing.py:127-229) on one frame already in
  * device memory (n >= 1 points, (n,3) f64).  Outputs (device, caller-allocated with n rows):
  *   mask (n) u8 inlier flag; colors, normals, compact_xyz (n,3) f64 of the inliers in input
- *   order (first n_in rows valid); labels (n) int64 over the inliers (ground -1);
- *   scalars (64 f64):
- *   [0] n_in  [1] n_ground  [2] n_nonground  [3] z_threshold  [4] eps  [5..10] x/y/z min,max
- *   [11..14] ground plane  [15] status (0 ok, 1 = no inliers -> reference IndexError)
- *   [16..18] 3-sigma mean  [19..21] std  [22..24] scaler mean  [25..27] scaler scale
- *   [28..33] scaled bbox  [39] n_clusters  [40] plane kind (0 lstsq, 1 min-z fallback,
- *   2 rank-deficient ground).  Asynchronous on `stream`. */
+ *   order (first LIDAR_S_N_IN rows valid); labels (n) int64 over the inliers (ground -1);
+ *   scalars (LIDAR_SCALARS f64): the LIDAR_S_* slots above, LIDAR_S_STATUS being
+ *   LIDAR_STATUS_OK or LIDAR_STATUS_NO_INLIER.  Asynchronous on `stream`. */
 int lidar_preprocess_f64(lidar_handle *h, const double *xyz, int64_t n, uint8_t *mask,
                          double *colors, double *normals, double *compact_xyz, int64_t *labels,
                          double *scalars, void *stream);
@@ -358,8 +378,8 @@ int lidar_preprocess_f64(lidar_handle *h, const double *xyz, int64_t n, uint8_t 
  * CSR layout).  xyz: the frames' rows concatenated; offsets: DEVICE int64[frames + 1] row
  * offsets (frame f = rows [offsets[f], offsets[f+1])); max_n >= every frame's size.  The
  * per-point outputs use the same row offsets (a frame's compact_xyz / labels rows start at
- * offsets[f] and run for its own n_in = scalars[f*64 + 0]); scalars holds 64 doubles per
- * frame, with [15] status: 0 ok, 1 no inlier (IndexError), 2 empty frame (ValueError). */
+ * offsets[f] and run for its own n_in = scalars[f*LIDAR_SCALARS + LIDAR_S_N_IN]); scalars holds
+ * LIDAR_SCALARS doubles per frame, LIDAR_S_STATUS being any of the three LIDAR_STATUS_* codes. */
 int lidar_preprocess_batch_f64(lidar_handle *h, const double *xyz, const int64_t *offsets, int32_t frames,
                                int64_t max_n, uint8_t *mask, double *colors, double *normals,
                                double *compact_xyz, int64_t *labels, double *scalars, void *stream);
@@ -368,7 +388,8 @@ int lidar_preprocess_batch_f64(lidar_handle *h, const double *xyz, const int64_t
  * app_with_db.py:80-141): lidar_preprocess_batch_f64's phases, then DBSCAN(eps,
  * min_samples=5) on the UNSCALED non-ground points (no StandardScaler / eps heuristic;
  * the reference passes eps = 0.3).  offsets == NULL: one frame of max_n points.  Same
- * outputs and status codes; scalars [22..27] = 0 / 1 and [28..33] = the unscaled bbox. */
+ * outputs and status codes; the scaler slots (LIDAR_S_SCALER_MEAN / _SCALE) hold 0 / 1 and
+ * LIDAR_S_SCALED_BBOX the unscaled bbox. */
 int lidar_preprocess_eps_batch_f64(lidar_handle *h, const double *xyz, const int64_t *offsets,
                                    int32_t frames, int64_t max_n, double eps, uint8_t *mask,
                                    double *colors, double *normals, double *compact_xyz,

@@ -15,6 +15,7 @@ reference behaviour exactly.
 import numpy as np
 
 from . import data_processing as dp
+from . import density_abi as abi
 
 
 class CrowdDensityModel:
@@ -41,29 +42,10 @@ class CrowdDensityModel:
     def analyze(self, processed_data):
         people = dp.extract_people_positions(processed_data)
         if len(people) == 0:
-            return {
-                "total_people": 0,
-                "avg_density": 0.0,
-                "max_density": 0.0,
-                "density_map": np.zeros((1, 1)),
-                "grid_coordinates": (np.array([0]), np.array([0])),
-                "density_values": np.array([0]),
-                "hotspots": [],
-            }
+            return abi.empty_result()
         dims = processed_data["dimensions"]
-        gx, gy, dens, flat_x, flat_y, stats, hot = dp._grid(people, dims["x_range"], dims["y_range"],
-                                                            self.grid_size)
-        flat = dens.flatten()
-        hotspots = [{"x": flat_x[i], "y": flat_y[i], "density": flat[i]} for i in hot]
-        res = {
-            "total_people": len(people),
-            "avg_density": np.float64(stats[1]),
-            "max_density": np.float64(stats[0]),
-            "density_map": dens,
-            "grid_coordinates": (flat_x, flat_y),
-            "density_values": flat,
-            "hotspots": hotspots,
-        }
+        rec = dp._grid(people, dims["x_range"], dims["y_range"], self.grid_size)
+        res = abi.analyze_result(len(people), *rec[2:])
         if self.backbone is not None:
             res["backbone_feature"] = self.encode(processed_data["points"])
             res["backbone_weights"] = "supplied" if self._weights is not None else "random-init"

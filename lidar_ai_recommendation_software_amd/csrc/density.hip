@@ -18,6 +18,7 @@
 // Sequential sums are one lane each (numpy's axis-0 order is sequential: reproducing it
 // bit for bit leaves no freedom); everything else is wave/workgroup parallel.
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -27,12 +28,15 @@ constexpr int kT = 1024;  // threads of the one-workgroup-per-frame kernels
 constexpr int kW = kT / 64;
 
 // ------------------------------------------------------------------ scalars layout
+// the public slots are lidar_amd.h's LIDAR_S_*; the rest are this file's own (and a LIDAR_PRE_DIAG
+// build's stamps at 48..57)
 enum : int {
-    S_NIN = 0, S_NGROUND = 1, S_NNG = 2, S_ZT = 3, S_EPS = 4, S_DIMS = 5,   // 5..10
-    S_PLANE = 11,                                                            // 11..14
-    S_STATUS = 15, S_MEAN = 16, S_STD = 19, S_SMEAN = 22, S_SSCALE = 25,
-    S_SLO = 28, S_SHI = 31, S_CELL = 34, S_CDIM = 35, S_NCELL = 38, S_NCLUST = 39,
-    S_PLANE_KIND = 40, S_N = 41, S_MINPTS = 42, S_COUNT = 64
+    S_NIN = LIDAR_S_N_IN, S_NGROUND = LIDAR_S_N_GROUND, S_NNG = LIDAR_S_N_NONGROUND, S_ZT = LIDAR_S_Z_THRESHOLD,
+    S_EPS = LIDAR_S_EPS, S_DIMS = LIDAR_S_DIMS, S_PLANE = LIDAR_S_PLANE, S_STATUS = LIDAR_S_STATUS,
+    S_MEAN = LIDAR_S_MEAN, S_STD = LIDAR_S_STD, S_SMEAN = LIDAR_S_SCALER_MEAN, S_SSCALE = LIDAR_S_SCALER_SCALE,
+    S_SLO = LIDAR_S_SCALED_BBOX, S_SHI = LIDAR_S_SCALED_BBOX + 3, S_NCLUST = LIDAR_S_N_CLUSTERS,
+    S_PLANE_KIND = LIDAR_S_PLANE_KIND, S_COUNT = LIDAR_SCALARS,
+    S_CELL = 34, S_CDIM = 35, S_NCELL = 38, S_N = 41, S_MINPTS = 42
 };
 
 // ------------------------------------------------------------------ frame batching
@@ -1850,46 +1854,34 @@ struct DbscanWs {
     int64_t max_cells, nblk_cells, nblk_pts;
 };
 
-constexpr int kDbscanParts = 13;
 int64_t max_cells_for(int64_t n) { return std::min<int64_t>(8 * n + 64, 1 << 22); }
 
-void plan_dbscan(lidar::Carver &cv, int64_t n, uint64_t *off)
-{
-    const int64_t mc = max_cells_for(n);
-    off[0] = cv.take<double>(P_COUNT);
-    off[1] = cv.take<uint32_t>(n);           // cid
-    off[2] = cv.take<uint32_t>(mc + 1);      // cellcnt
-    off[3] = cv.take<uint32_t>(mc + 1);      // cellstart
-    off[4] = cv.take<uint32_t>(mc + 1);      // fill
-    off[5] = cv.take<uint32_t>(n + 1);       // order
-    off[6] = cv.take<uint32_t>(n + 1);       // flag
-    off[7] = cv.take<uint32_t>(n + 1);       // rank
-    off[8] = cv.take<uint32_t>(4 * kT);      // partial
-    off[9] = cv.take<double>(3 * n);         // sxyz
-    off[10] = cv.take<int32_t>(n);           // cnt
-    off[11] = cv.take<int32_t>(n);           // parent
-    off[12] = cv.take<uint8_t>(n);           // core (sorted slots)
-}
-
-DbscanWs bind_dbscan(char *base, const uint64_t *off, int64_t n)
+// The DBSCAN workspace of one frame of n points: every sub-buffer is named, typed and sized here,
+// in carve order.  Called twice from the same carver position: with base == nullptr to size the
+// allocation (cv.off afterwards), then with the allocation for the pointers.
+DbscanWs carve_dbscan(lidar::Carver &cv, int64_t n, char *base)
 {
     DbscanWs w;
-    w.P = reinterpret_cast<double *>(base + off[0]);
-    w.cid = reinterpret_cast<uint32_t *>(base + off[1]);
-    w.cellcnt = reinterpret_cast<uint32_t *>(base + off[2]);
-    w.cellstart = reinterpret_cast<uint32_t *>(base + off[3]);
-    w.fill = reinterpret_cast<uint32_t *>(base + off[4]);
-    w.order = reinterpret_cast<uint32_t *>(base + off[5]);
-    w.flag = reinterpret_cast<uint32_t *>(base + off[6]);
-    w.rank = reinterpret_cast<uint32_t *>(base + off[7]);
-    w.partial = reinterpret_cast<uint32_t *>(base + off[8]);
-    w.sxyz = reinterpret_cast<double *>(base + off[9]);
-    w.cnt = reinterpret_cast<int32_t *>(base + off[10]);
-    w.parent = reinterpret_cast<int32_t *>(base + off[11]);
-    w.core = reinterpret_cast<uint8_t *>(base + off[12]);
+    auto part = [&](auto *&p, uint64_t count) {
+        using T = std::remove_reference_t<decltype(*p)>;
+        p = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + cv.take<T>(count));
+    };
     w.max_cells = max_cells_for(n);
     w.nblk_cells = (w.max_cells + 1 + kScanPer - 1) / kScanPer;
     w.nblk_pts = (n + 1 + kScanPer - 1) / kScanPer;
+    part(w.P, P_COUNT);
+    part(w.cid, n);
+    part(w.cellcnt, w.max_cells + 1);
+    part(w.cellstart, w.max_cells + 1);
+    part(w.fill, w.max_cells + 1);
+    part(w.order, n + 1);
+    part(w.flag, n + 1);
+    part(w.rank, n + 1);
+    part(w.partial, 4 * kT);
+    part(w.sxyz, 3 * n);
+    part(w.cnt, n);
+    part(w.parent, n);
+    part(w.core, n);
     return w;
 }
 
@@ -1976,15 +1968,15 @@ int run_preprocess(lidar_handle *h, const double *xyz, int64_t n, const int64_t 
     const uint64_t o_sc = cv.take<double>(3 * n);
     const uint64_t o_pos = cv.take<int32_t>(n);
     const uint64_t o_lab = cv.take<int64_t>(n);
-    uint64_t off[kDbscanParts];
-    plan_dbscan(cv, n, off);
+    lidar::Carver at = cv;  // where the DBSCAN sub-buffers start
+    carve_dbscan(cv, n, nullptr);
     const uint64_t wss = lidar::align_up(cv.off, 256);
     char *base = static_cast<char *>(lidar::workspace(h, wss * (uint64_t)frames));
     if (!base) return LIDAR_ENOMEM;
     double *sc = reinterpret_cast<double *>(base + o_sc);
     int32_t *ng_pos = reinterpret_cast<int32_t *>(base + o_pos);
     int64_t *ng_lab = reinterpret_cast<int64_t *>(base + o_lab);
-    DbscanWs w = bind_dbscan(base, off, n);
+    DbscanWs w = carve_dbscan(at, n, base);
     FrameMap fm;
     fm.wss = (int64_t)wss;
     fm.offs = offs;
@@ -2007,6 +1999,27 @@ int run_preprocess(lidar_handle *h, const double *xyz, int64_t n, const int64_t 
     return LIDAR_OK;
 }
 
+// DBSCAN on the caller's own points (lidar_dbscan_f64, lidar_radius_count_f64): the workspace of one
+// frame, its parameter block and bounding box, then run_dbscan.  The block is staged in the
+// handle's pinned buffer, which the next call reuses: the caller synchronises s before it returns.
+int run_dbscan_on(lidar_handle *h, const double *x, int64_t n, double eps, int32_t min_samples, int64_t *labels,
+                  hipStream_t s, bool count_only, bool exact_counts, DbscanWs &w)
+{
+    lidar::Carver size, cv;
+    carve_dbscan(size, n, nullptr);
+    char *base = static_cast<char *>(lidar::workspace(h, size.off));
+    if (!base) return LIDAR_ENOMEM;
+    w = carve_dbscan(cv, n, base);
+    double *hp = static_cast<double *>(h->host_pinned);
+    for (int i = 0; i < P_COUNT; ++i) hp[i] = 0.0;
+    hp[P_N] = (double)n;
+    hp[P_EPS] = eps;
+    hp[P_ACTIVE] = 1.0;
+    HIP_TRY(hipMemcpyAsync(w.P, hp, sizeof(double) * P_COUNT, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(1), dim3(kT), 0, s, x, w.P, FrameMap{});
+    return run_dbscan(h, x, n, min_samples, w, labels, s, FrameMap{}, 1, count_only, exact_counts);
+}
+
 }  // namespace
 
 // ====================================================================== C-ABI
@@ -2020,23 +2033,11 @@ LIDAR_EXPORT int lidar_dbscan_f64(lidar_handle *h, const double *x, int64_t n, d
     if (n == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    lidar::Carver cv;
-    uint64_t off[kDbscanParts];
-    plan_dbscan(cv, n, off);
-    char *base = static_cast<char *>(lidar::workspace(h, cv.off));
-    if (!base) return LIDAR_ENOMEM;
-    DbscanWs w = bind_dbscan(base, off, n);
-    double hp[P_COUNT] = {};
-    hp[P_N] = (double)n;
-    hp[P_EPS] = eps;
-    hp[P_ACTIVE] = 1.0;
-    HIP_TRY(hipMemcpyAsync(w.P, hp, sizeof hp, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(1), dim3(kT), 0, s, x, w.P, FrameMap{});
-    int rc = run_dbscan(h, x, n, min_samples, w, labels, s, FrameMap{}, 1, false, counts != nullptr);
+    DbscanWs w;
+    int rc = run_dbscan_on(h, x, n, eps, min_samples, labels, s, false, counts != nullptr, w);
     if (rc) return rc;
     if (counts) HIP_TRY(hipMemcpyAsync(counts, w.cnt, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, s));
-    // hp is a stack buffer: make sure the H2D copy has consumed it
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));  // the pinned parameter block is reused by the next call
     return LIDAR_OK;
 }
 
@@ -2233,21 +2234,9 @@ LIDAR_EXPORT int lidar_radius_count_f64(lidar_handle *h, const double *x, int64_
     if (n == 0) return LIDAR_OK;
     ON_DEVICE(h->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    lidar::Carver cv;
-    uint64_t off[kDbscanParts];
-    plan_dbscan(cv, n, off);
-    char *base = static_cast<char *>(lidar::workspace(h, cv.off));
-    if (!base) return LIDAR_ENOMEM;
-    DbscanWs w = bind_dbscan(base, off, n);
-    double *hp = static_cast<double *>(h->host_pinned);
-    for (int i = 0; i < P_COUNT; ++i) hp[i] = 0.0;
-    hp[P_N] = (double)n;
+    DbscanWs w;
     // r = 0: a tiny positive cell size keeps the grid finite; only exact duplicates count
-    hp[P_EPS] = r > 0.0 ? r : 1e-300;
-    hp[P_ACTIVE] = 1.0;
-    HIP_TRY(hipMemcpyAsync(w.P, hp, sizeof(double) * P_COUNT, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(dbscan_bbox_kernel, dim3(1), dim3(kT), 0, s, x, w.P, FrameMap{});
-    int rc = run_dbscan(h, x, n, 1, w, nullptr, s, FrameMap{}, 1, true);
+    int rc = run_dbscan_on(h, x, n, r > 0.0 ? r : 1e-300, 1, nullptr, s, true, false, w);
     if (rc) return rc;
     hipLaunchKernelGGL(widen_counts_kernel, dim3(point_blocks(n, 1)), dim3(256), 0, s, w.cnt, n, counts);
     LAUNCH_CHECK();

@@ -19,6 +19,7 @@ import weakref
 import numpy as np
 
 from . import _native as nat
+from . import density_abi as abi
 
 # ----------------------------------------------------------------- device cache
 # Arrays this module returned keep their device copy, so that extract_people_positions /
@@ -234,43 +235,23 @@ def preprocess_lidar_data(points):
     n = len(pts)
     is_int = pts.dtype.kind in "iub"
     x = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64)).cuda()
-    dev = x.device
-    mask = torch.empty(n, dtype=torch.uint8, device=dev)
-    colors = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    normals = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    comp = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    labels = torch.empty(n, dtype=torch.int64, device=dev)
-    scal = torch.empty(64, dtype=torch.float64, device=dev)
-    nat.call("lidar_preprocess_f64", _handle(), nat.ptr(x), n, nat.ptr(mask), nat.ptr(colors),
-             nat.ptr(normals), nat.ptr(comp), nat.ptr(labels), nat.ptr(scal), nat.stream_ptr())
-    S = scal.cpu().numpy()
-    if S[15] != 0:
-        raise IndexError("index -1 is out of bounds for axis 0 with size 0")
-    nin = int(S[0])
-    comp_d, lab_d = comp[:nin], labels[:nin]
+    o = abi.preprocess_outputs(n, x.device)
+    abi.preprocess(_handle(), x, None, 1, n, None, o, nat.stream_ptr())
+    S = o["scal"].cpu().numpy()
+    abi.raise_for_status(S[abi.S_STATUS])
+    nin = int(S[abi.S_N_IN])
+    comp_d, lab_d = o["comp"][:nin], o["labels"][:nin]
     inl = comp_d.cpu().numpy()
     if is_int:
         inl = inl.astype(pts.dtype)
-    cols = colors[:nin].cpu().numpy()
-    nrm = normals[:nin].cpu().numpy()
+    cols = o["colors"][:nin].cpu().numpy()
+    nrm = o["normals"][:nin].cpu().numpy()
     if is_int:
         nrm = nrm.astype(pts.dtype)
     clusters = lab_d.cpu().numpy()
-    kind = S[40]
-    if kind == 1.0 and is_int:
-        plane = np.array([0, 0, 1, -int(S[9])])
-    elif kind == 1.0:
-        plane = np.array([0.0, 0.0, 1.0, S[14]])
-    else:
-        plane = np.array([S[11], S[12], -1, S[14]], dtype=np.float64)
-    mins, maxs = S[[5, 7, 9]], S[[6, 8, 10]]
-    if is_int:
-        mins, maxs = mins.astype(pts.dtype), maxs.astype(pts.dtype)
-    (x_min, y_min, z_min), (x_max, y_max, z_max) = mins, maxs
-    dims = {"x_range": (x_min, x_max), "y_range": (y_min, y_max), "z_range": (z_min, z_max),
-            "width": x_max - x_min, "length": y_max - y_min, "height": z_max - z_min}
     out = {"points": inl, "colors": cols, "normals": nrm, "clusters": clusters,
-           "ground_plane": plane, "dimensions": dims}
+           "ground_plane": abi.ground_plane(S, is_int),
+           "dimensions": abi.dimensions(S, pts.dtype if is_int else None)}
     _remember(inl, comp_d)
     _remember(clusters, lab_d)
     return out
@@ -323,16 +304,11 @@ def extract_people_positions(processed_data):
         return np.array([])
     x = _on_device(pts, torch.float64)
     lbl = _on_device(lab, torch.int64)
-    people = torch.empty((n, 2), dtype=torch.float64, device=x.device)
-    k = nat.I64(0)
-    import ctypes
-    nat.call("lidar_people_f64", _handle(), nat.ptr(x), nat.ptr(lbl), n, nat.ptr(people), ctypes.byref(k),
-             nat.stream_ptr())
-    k = k.value
+    people_d, k = abi.people(_handle(), x, lbl, n, nat.stream_ptr())
     if k == 0:
         return np.array([])
-    out = people[:k].cpu().numpy()
-    _remember(out, people[:k])
+    out = people_d.cpu().numpy()
+    _remember(out, people_d)
     return out
 
 
@@ -346,16 +322,12 @@ def _grid(people_positions, x_range, y_range, grid_size):
     with nat.grid_alloc():
         gx = torch.empty(nx, dtype=torch.float64, device=dev)
         gy = torch.empty(ny, dtype=torch.float64, device=dev)
-        buf = torch.empty(3 * nx * ny + 13, dtype=torch.float64, device=dev)
+        buf = torch.empty(abi.record_doubles(nx, ny, edges=False), dtype=torch.float64, device=dev)
     nat.call("lidar_density_grid_f64", _handle(), nat.ptr(p), len(p), float(x_min), float(x_max),
              float(y_min), float(y_max), float(grid_size), nx, ny, nat.ptr(gx), nat.ptr(gy), nat.ptr(buf),
              nat.stream_ptr())
-    b = buf.cpu().numpy()
-    m = nx * ny
-    dens = b[:m].reshape(nx, ny)
-    stats = b[3 * m:3 * m + 8]
-    hot = b[3 * m + 8:3 * m + 13].view(np.int64)[: int(stats[3])]
-    return gx.cpu().numpy(), gy.cpu().numpy(), dens, b[m:2 * m], b[2 * m:3 * m], stats, hot
+    rec = abi.decode_record(buf.cpu().numpy(), nx, ny, edges=False)
+    return (gx.cpu().numpy(), gy.cpu().numpy()) + rec[2:]
 
 
 def calculate_grid_density(people_positions, x_range, y_range, grid_size=1.0):

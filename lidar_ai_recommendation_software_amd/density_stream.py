@@ -14,13 +14,13 @@ layout: ``lidar_preprocess_batch_f64`` / ``lidar_people_batch_f64`` /
 return per frame the reference's ``analyze`` result (the big per-point arrays stay on
 the device).  Results are the drop-in path's, bit for bit (same kernels).
 """
-import ctypes
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _native as nat
+from . import density_abi as abi
 from .streams import side_streams
 
 
@@ -58,63 +58,42 @@ class DensityStream:
     def _buffers(self, w, n):
         b = self._bufs[w]
         if b.get("n", 0) < n:
-            d = self.device
-            b.update(n=n, mask=torch.empty(n, dtype=torch.uint8, device=d),
-                     colors=torch.empty((n, 3), dtype=torch.float64, device=d),
-                     normals=torch.empty((n, 3), dtype=torch.float64, device=d),
-                     comp=torch.empty((n, 3), dtype=torch.float64, device=d),
-                     labels=torch.empty(n, dtype=torch.int64, device=d),
-                     people=torch.empty((n, 2), dtype=torch.float64, device=d),
-                     scal=torch.empty(64, dtype=torch.float64, device=d))
+            b.update(abi.preprocess_outputs(n, self.device), n=n,
+                     people=torch.empty((n, 2), dtype=torch.float64, device=self.device))
         return b
 
     def analyze_frame(self, x, w=0):
         """x: (n, 3) float64 CUDA tensor -> (result dict of CrowdDensityModel.analyze,
         device tensors {points, colors, normals, clusters} of the preprocessed frame)."""
         n = x.shape[0]
-        if n == 0:
-            raise ValueError("zero-size array to reduction operation minimum which has no identity")
+        if n == 0:  # decided before any launch
+            abi.raise_for_status(abi.STATUS_EMPTY)
         b = self._buffers(w, n)
         s = self._streams[w]
         h = nat.handle(self.device.index, slot=8 + w)
         sp = s.cuda_stream
-        nat.call("lidar_preprocess_f64", h, nat.ptr(x), n, nat.ptr(b["mask"]), nat.ptr(b["colors"]),
-                 nat.ptr(b["normals"]), nat.ptr(b["comp"]), nat.ptr(b["labels"]), nat.ptr(b["scal"]), sp)
-        S = np.empty(64)
+        abi.preprocess(h, x, None, 1, n, None, b, sp)
+        S = np.empty(abi.SCALARS)
         with torch.cuda.stream(s):
             S[:] = b["scal"].cpu().numpy()
-        if S[15] != 0:
-            raise IndexError("index -1 is out of bounds for axis 0 with size 0")
-        nin = int(S[0])
+        abi.raise_for_status(S[abi.S_STATUS])
+        nin = int(S[abi.S_N_IN])
         frame = {"points": b["comp"][:nin], "colors": b["colors"][:nin], "normals": b["normals"][:nin],
                  "clusters": b["labels"][:nin]}
-        k = nat.I64(0)
-        nat.call("lidar_people_f64", h, nat.ptr(b["comp"]), nat.ptr(b["labels"]), nin, nat.ptr(b["people"]),
-                 ctypes.byref(k), sp)
-        k = k.value
+        _, k = abi.people(h, b["comp"], b["labels"], nin, sp, out=b["people"])
         if k == 0:
-            return {"total_people": 0, "avg_density": 0.0, "max_density": 0.0, "density_map": np.zeros((1, 1)),
-                    "grid_coordinates": (np.array([0]), np.array([0])), "density_values": np.array([0]),
-                    "hotspots": []}, frame
-        x_min, x_max, y_min, y_max = S[5], S[6], S[7], S[8]
+            return abi.empty_result(), frame
+        x_min, x_max, y_min, y_max = abi.xy_extent(S)
         nx, ny = nat.grid_dims(x_min, x_max, y_min, y_max, self.grid_size)
-        m = nx * ny
         with torch.cuda.stream(s), nat.grid_alloc():
             gx = torch.empty(nx, dtype=torch.float64, device=self.device)
             gy = torch.empty(ny, dtype=torch.float64, device=self.device)
-            buf = torch.empty(3 * m + 13, dtype=torch.float64, device=self.device)
+            buf = torch.empty(abi.record_doubles(nx, ny, edges=False), dtype=torch.float64, device=self.device)
         nat.call("lidar_density_grid_f64", h, nat.ptr(b["people"]), k, float(x_min), float(x_max), float(y_min),
                  float(y_max), self.grid_size, nx, ny, nat.ptr(gx), nat.ptr(gy), nat.ptr(buf), sp)
         with torch.cuda.stream(s):
             hb = buf.cpu().numpy()
-        dens = hb[:m].reshape(nx, ny)
-        flat_x, flat_y, stats = hb[m:2 * m], hb[2 * m:3 * m], hb[3 * m:3 * m + 8]
-        hot = hb[3 * m + 8:3 * m + 13].view(np.int64)[: int(stats[3])]
-        flat = dens.flatten()
-        res = {"total_people": k, "avg_density": np.float64(stats[1]), "max_density": np.float64(stats[0]),
-               "density_map": dens, "grid_coordinates": (flat_x, flat_y), "density_values": flat,
-               "hotspots": [{"x": flat_x[i], "y": flat_y[i], "density": flat[i]} for i in hot]}
-        return res, frame
+        return abi.analyze_result(k, *abi.decode_record(hb, nx, ny, edges=False)[2:]), frame
 
     def run(self, frames):
         """frames: list of (n_i, 3) float64 CUDA tensors -> list of analyze results, in order.
@@ -230,41 +209,33 @@ class DensityStream:
         rows = max(1, total)
         f64 = dict(dtype=torch.float64, device=dev)
         offs = torch.from_numpy(offs_h).to(dev)
-        mask = torch.empty(rows, dtype=torch.uint8, device=dev)
-        colors, normals, comp = (torch.empty((rows, 3), **f64) for _ in range(3))
-        labels = torch.empty(rows, dtype=torch.int64, device=dev)
-        scal = torch.empty((F, 64), **f64)
+        o = abi.preprocess_outputs(rows, dev, frames=F)
         h = nat.handle(self.device.index, slot=self.BATCH_SLOT)
         sp = torch.cuda.current_stream(dev).cuda_stream
-        nat.call("lidar_preprocess_batch_f64", h, nat.ptr(x), nat.ptr(offs), F, max_n, nat.ptr(mask),
-                 nat.ptr(colors), nat.ptr(normals), nat.ptr(comp), nat.ptr(labels), nat.ptr(scal), sp)
+        abi.preprocess(h, x, offs, F, max_n, None, o, sp)
         people = torch.empty((rows, 2), **f64)
         kdev = torch.empty(F, dtype=torch.int64, device=dev)
-        nat.call("lidar_people_batch_f64", h, nat.ptr(comp), nat.ptr(labels), nat.ptr(offs), F, max_n,
-                 nat.ptr(scal), nat.ptr(people), nat.ptr(kdev), sp)
-        S = scal.cpu().numpy()  # read-back 1 (also waits for people)
-        for f in range(F):
-            if S[f, 15] == 2.0:
-                raise ValueError("zero-size array to reduction operation minimum which has no identity")
-            if S[f, 15] != 0.0:
-                raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+        nat.call("lidar_people_batch_f64", h, nat.ptr(o["comp"]), nat.ptr(o["labels"]), nat.ptr(offs), F, max_n,
+                 nat.ptr(o["scal"]), nat.ptr(people), nat.ptr(kdev), sp)
+        S = o["scal"].cpu().numpy()  # read-back 1 (also waits for people)
+        status = S[:, abi.S_STATUS]
+        for bad in status[status != abi.STATUS_OK]:  # the first failing frame's exception
+            abi.raise_for_status(bad)
         K = kdev.cpu().numpy()  # read-back 2
         last_people = (people, offs_h, K)
+        counts = K.tolist()
         jobs = np.zeros((F, 8), dtype=np.float64)
         out_off = scr_off = 0
-        dims = []
+        dims = [None] * F
         for f in range(F):
-            if K[f] <= 0:
-                dims.append(None)
+            if counts[f] <= 0:
                 continue
-            x_min, x_max, y_min, y_max = S[f, 5], S[f, 6], S[f, 7], S[f, 8]
+            x_min, x_max, y_min, y_max = abi.xy_extent(S[f])
             nx, ny = nat.grid_dims(x_min, x_max, y_min, y_max, self.grid_size)
-            m = nx * ny
-            g2 = self.grid_size * 2.0
-            jobs[f] = (x_min - g2, y_min - g2, self.grid_size, nx, ny, out_off, scr_off, 0)
-            dims.append((nx, ny, out_off))
-            out_off += nx + ny + 3 * m + 13
-            scr_off += m + (m + 1) // 2 + nx + ny + 2
+            jobs[f] = abi.job_row(x_min, y_min, self.grid_size, nx, ny, out_off, scr_off)
+            dims[f] = (nx, ny, out_off)
+            out_off += abi.record_doubles(nx, ny, True)
+            scr_off += abi.scratch_doubles(nx, ny)
         res = [None] * F
         if out_off:
             jd = torch.from_numpy(jobs).to(dev)
@@ -275,20 +246,8 @@ class DensityStream:
             ob = out.cpu().numpy()  # read-back 3
         for f in range(F):
             if dims[f] is None:
-                res[f] = {"total_people": 0, "avg_density": 0.0, "max_density": 0.0,
-                          "density_map": np.zeros((1, 1)), "grid_coordinates": (np.array([0]), np.array([0])),
-                          "density_values": np.array([0]), "hotspots": []}
+                res[f] = abi.empty_result()
                 continue
-            nx, ny, o = dims[f]
-            m = nx * ny
-            b = ob[o:o + nx + ny + 3 * m + 13]
-            dens = b[nx + ny:nx + ny + m].reshape(nx, ny)
-            flat_x, flat_y = b[nx + ny + m:nx + ny + 2 * m], b[nx + ny + 2 * m:nx + ny + 3 * m]
-            stats = b[nx + ny + 3 * m:nx + ny + 3 * m + 8]
-            hot = b[nx + ny + 3 * m + 8:nx + ny + 3 * m + 13].view(np.int64)[: int(stats[3])]
-            flat = dens.flatten()
-            res[f] = {"total_people": int(K[f]), "avg_density": np.float64(stats[1]),
-                      "max_density": np.float64(stats[0]), "density_map": dens,
-                      "grid_coordinates": (flat_x, flat_y), "density_values": flat,
-                      "hotspots": [{"x": flat_x[i], "y": flat_y[i], "density": flat[i]} for i in hot]}
+            nx, ny, off = dims[f]
+            res[f] = abi.analyze_result(counts[f], *abi.decode_record(ob, nx, ny, True, off)[2:])
         return res, last_people

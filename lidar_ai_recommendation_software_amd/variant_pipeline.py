@@ -18,11 +18,10 @@ and return the reference's dicts, bit for bit (``tests/test_gpu_tier_r.py``).  H
 the reference's own scalar glue on tiny arrays (the grid edges ``np.arange``, the hotspot
 sort over <= a few thousand cells).
 """
-import ctypes
-
 import numpy as np
 
 from . import _native as nat
+from . import density_abi as abi
 from .data_processing import _handle, _on_device, _reference_shape_errors, _remember
 
 EPS = 0.3          # app_simplified.py:107
@@ -42,34 +41,21 @@ def preprocess_point_cloud(points, eps=EPS):
     n = len(pts)
     is_int = pts.dtype.kind in "iub"
     x = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64)).cuda()
-    dev = x.device
-    mask = torch.empty(n, dtype=torch.uint8, device=dev)
-    colors = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    normals = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    comp = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    labels = torch.empty(n, dtype=torch.int64, device=dev)
-    scal = torch.empty(64, dtype=torch.float64, device=dev)
-    nat.call("lidar_preprocess_eps_batch_f64", _handle(), nat.ptr(x), None, 1, n, float(eps), nat.ptr(mask),
-             nat.ptr(colors), nat.ptr(normals), nat.ptr(comp), nat.ptr(labels), nat.ptr(scal), nat.stream_ptr())
-    S = scal.cpu().numpy()
-    if S[15] != 0:
-        raise IndexError("index -1 is out of bounds for axis 0 with size 0")
-    nin = int(S[0])
-    comp_d, lab_d = comp[:nin], labels[:nin]
+    o = abi.preprocess_outputs(n, x.device)
+    abi.preprocess(_handle(), x, None, 1, n, float(eps), o, nat.stream_ptr())
+    S = o["scal"].cpu().numpy()
+    abi.raise_for_status(S[abi.S_STATUS])
+    nin = int(S[abi.S_N_IN])
+    comp_d, lab_d = o["comp"][:nin], o["labels"][:nin]
     inl = comp_d.cpu().numpy()
     if is_int:
         inl = inl.astype(pts.dtype)
-    cols = colors[:nin].cpu().numpy()
+    cols = o["colors"][:nin].cpu().numpy()
     clusters = lab_d.cpu().numpy()
-    mins, maxs = S[[5, 7, 9]], S[[6, 8, 10]]
-    if is_int:
-        mins, maxs = mins.astype(pts.dtype), maxs.astype(pts.dtype)
-    (x_min, y_min, z_min), (x_max, y_max, z_max) = mins, maxs
-    dims = {"x_range": (x_min, x_max), "y_range": (y_min, y_max), "z_range": (z_min, z_max),
-            "width": x_max - x_min, "length": y_max - y_min, "height": z_max - z_min}
     _remember(inl, comp_d)
     _remember(clusters, lab_d)
-    return {"points": inl, "colors": cols, "clusters": clusters, "dimensions": dims}
+    return {"points": inl, "colors": cols, "clusters": clusters,
+            "dimensions": abi.dimensions(S, pts.dtype if is_int else None)}
 
 
 def _people(points, clusters):
@@ -80,11 +66,7 @@ def _people(points, clusters):
         return np.zeros((0, 2)), None
     x = _on_device(points, torch.float64)
     lbl = _on_device(clusters, torch.int64)
-    people = torch.empty((n, 2), dtype=torch.float64, device=x.device)
-    k = nat.I64(0)
-    nat.call("lidar_people_f64", _handle(), nat.ptr(x), nat.ptr(lbl), n, nat.ptr(people), ctypes.byref(k),
-             nat.stream_ptr())
-    return people[:k.value], k.value
+    return abi.people(_handle(), x, lbl, n, nat.stream_ptr())
 
 
 def analyze_crowd_density(processed_data):
