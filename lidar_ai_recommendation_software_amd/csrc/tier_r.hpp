@@ -1,0 +1,174 @@
+// tier_r.hpp — what two of preprocess.hip, dbscan.hip and density_grid.hip share: sizes, the scalars slots,
+// the frame map, fp64 rounding wrappers, workgroup min / max / scan, the DBSCAN workspace and dbscan.hip's
+// host entry points for preprocess.hip.  Kernels stay local to their translation unit.
+#pragma once
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+
+namespace lidar {
+namespace tier_r {
+
+constexpr int kT = 1024;  // threads of the one-workgroup-per-frame kernels
+constexpr int kW = kT / 64;
+
+// ------------------------------------------------------------------ scalars layout
+// the public slots are lidar_amd.h's LIDAR_S_*; the rest are Tier R's own (and a LIDAR_PRE_DIAG
+// build's stamps at 48..57)
+enum : int {
+    S_NIN = LIDAR_S_N_IN, S_NGROUND = LIDAR_S_N_GROUND, S_NNG = LIDAR_S_N_NONGROUND, S_ZT = LIDAR_S_Z_THRESHOLD,
+    S_EPS = LIDAR_S_EPS, S_DIMS = LIDAR_S_DIMS, S_PLANE = LIDAR_S_PLANE, S_STATUS = LIDAR_S_STATUS,
+    S_MEAN = LIDAR_S_MEAN, S_STD = LIDAR_S_STD, S_SMEAN = LIDAR_S_SCALER_MEAN, S_SSCALE = LIDAR_S_SCALER_SCALE,
+    S_SLO = LIDAR_S_SCALED_BBOX, S_SHI = LIDAR_S_SCALED_BBOX + 3, S_NCLUST = LIDAR_S_N_CLUSTERS,
+    S_PLANE_KIND = LIDAR_S_PLANE_KIND, S_COUNT = LIDAR_SCALARS,
+    S_CELL = 34, S_CDIM = 35, S_NCELL = 38, S_N = 41, S_MINPTS = 42
+};
+
+// ------------------------------------------------------------------ frame batching
+// Every Tier R kernel runs one frame per blockIdx.y.  Frame f's scratch lives at
+// f * wss bytes into one workspace allocation (same sub-buffer offsets in every frame),
+// its rows of the caller's arrays start at row offs[f] (CSR; offs == nullptr: a single
+// frame of the given n), and its scalars at S + f * S_COUNT.
+struct FrameMap {
+    int64_t wss = 0;
+    const int64_t *offs = nullptr;
+    template <class T> __device__ __forceinline__ T *ws(T *p) const
+    {
+        return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)((int64_t)blockIdx.y * wss));
+    }
+    template <class T> __device__ __forceinline__ T *rows(T *p, int width) const
+    {
+        return offs ? p + offs[blockIdx.y] * width : p;
+    }
+    __device__ __forceinline__ int64_t n(int64_t single) const
+    {
+        return offs ? offs[blockIdx.y + 1] - offs[blockIdx.y] : single;
+    }
+    template <class T> __device__ __forceinline__ T *scal(T *S) const { return S + (int64_t)blockIdx.y * S_COUNT; }
+};
+
+__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
+
+// ---- workgroup helpers (1024 threads)
+struct BlockScratch {
+    double d[6][kW];
+    uint32_t i[kW];
+    double bc[16];  // broadcast
+    double chain[6];  // block_sum_chain results: [accumulator * 3 + column]
+};
+
+// workgroup reduction of v with op (fmin or fmax, through row `SLOT` of s.d): every thread gets the result
+template <int SLOT, class Op>
+__device__ __forceinline__ double block_reduce(BlockScratch &s, double v, Op op)
+{
+    for (int m = 32; m >= 1; m >>= 1) v = op(v, __shfl_xor(v, m, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s.d[SLOT][threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = s.d[SLOT][0];
+    for (int w = 1; w < kW; ++w) r = op(r, s.d[SLOT][w]);
+    return r;
+}
+__device__ __forceinline__ double block_min(BlockScratch &s, double v)
+{
+    return block_reduce<0>(s, v, [](double a, double b) { return fmin(a, b); });
+}
+__device__ __forceinline__ double block_max(BlockScratch &s, double v)
+{
+    return block_reduce<1>(s, v, [](double a, double b) { return fmax(a, b); });
+}
+// bounding box of the rows [0, n) of a row-major (n, 3) array, stored to lo_out[0..2] / hi_out[0..2]
+__device__ __forceinline__ void block_bbox(BlockScratch &s, const double *x, int64_t n, double *lo_out, double *hi_out)
+{
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t i = threadIdx.x; i < n; i += kT)
+        for (int c = 0; c < 3; ++c) {
+            lo[c] = fmin(lo[c], x[3 * i + c]);
+            hi[c] = fmax(hi[c], x[3 * i + c]);
+        }
+    for (int c = 0; c < 3; ++c) {
+        const double a = block_min(s, lo[c]), b = block_max(s, hi[c]);
+        if (threadIdx.x == 0) {
+            lo_out[c] = a;
+            hi_out[c] = b;
+        }
+    }
+}
+// exclusive scan of one 32-bit count per thread over the workgroup's waves from w0 on (0: the whole
+// workgroup): the sum of v over the threads of waves w0 .. this one that come before the caller.
+// wtot: kW words of LDS, free again after the caller's next barrier.
+__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t *wtot, int w0 = 0)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t incl = (uint32_t)wave_incl_scan_i32((int)v);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = w0; w < wave; ++w) base += wtot[w];
+    return base + incl - v;
+}
+
+// ------------------------------------------------------------------ DBSCAN workspace
+// One frame's DBSCAN buffers (carve_dbscan names, types and sizes them) and the points x they
+// cluster: the preprocess path's scaled cloud inside the same workspace, or the caller's own array
+// (a single frame, wss == 0).  Passed to every DBSCAN kernel by value.
+struct DbscanWs {
+    const double *x;
+    double *P;
+    uint32_t *cid, *cellcnt, *cellstart, *fill, *order, *flag, *rank, *partial;
+    double *sxyz;
+    int32_t *cnt, *parent;
+    uint8_t *core;  // per sorted slot; `fill` doubles as the cells' smallest core index after the scatter
+    int64_t max_cells, nblk_cells, nblk_pts;
+    // frame blockIdx.y's view: every buffer at the same offset of that frame's wss bytes
+    __device__ __forceinline__ DbscanWs frame(const FrameMap &fm) const
+    {
+        DbscanWs f = *this;
+        f.x = fm.ws(x);
+        f.P = fm.ws(P);
+        f.cid = fm.ws(cid);
+        f.cellcnt = fm.ws(cellcnt);
+        f.cellstart = fm.ws(cellstart);
+        f.fill = fm.ws(fill);
+        f.order = fm.ws(order);
+        f.flag = fm.ws(flag);
+        f.rank = fm.ws(rank);
+        f.partial = fm.ws(partial);
+        f.sxyz = fm.ws(sxyz);
+        f.cnt = fm.ws(cnt);
+        f.parent = fm.ws(parent);
+        f.core = fm.ws(core);
+        return f;
+    }
+};
+
+inline int64_t max_cells_for(int64_t n) { return std::min<int64_t>(8 * n + 64, 1 << 22); }
+
+// blocks per frame of a per-point kernel: enough to fill the chip across all frames
+inline unsigned point_blocks(int64_t nmax, int frames)
+{
+    const int64_t cap = std::max<int64_t>(8, 4096 / std::max(1, frames));
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((nmax + 255) / 256, cap));
+}
+
+// ---- dbscan.hip, for the preprocess path
+// The DBSCAN workspace of one frame of n points, in carve order.  Called twice from the same carver
+// position: with base == nullptr to size the allocation (cv.off afterwards), then with the
+// allocation for the pointers.  w.x is the caller's to set.
+DbscanWs carve_dbscan(Carver &cv, int64_t n, char *base);
+// every frame's parameter block P from its preprocess scalars (point count, eps, scaled bbox)
+void dbscan_params_from_scalars(const double *scalars, const DbscanWs &w, hipStream_t s, FrameMap fm, int frames);
+// the DBSCAN pipeline on w.x (P[P_N] points, eps P[P_EPS], bbox in P) -> labels, for every frame
+// exact_counts: cnt[i] is the full eps-neighbour count (radius counts, the standalone API's
+// counts output); otherwise counting stops at min_samples.  h: profiling spans (may be null).
+int run_dbscan(lidar_handle *h, int64_t nmax, int32_t min_samples, const DbscanWs &w, int64_t *labels, hipStream_t s,
+               FrameMap fm, int frames, bool count_only = false, bool exact_counts = false);
+// every frame's cluster count, from P into its scalars
+void dbscan_nclust_to_scalars(const DbscanWs &w, double *scalars, hipStream_t s, FrameMap fm, int frames);
+
+}  // namespace tier_r
+}  // namespace lidar

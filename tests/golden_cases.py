@@ -97,7 +97,7 @@ def check_plane(name, got, want, inliers):
     """The ground plane vs the reference's ``lstsq(rcond=None)`` plane (data_processing.py:169-183).
 
     gelsd is a backward-stable solver whose roundings are not reproducible, so the device (TSQR +
-    Jacobi SVD, density.hip plane_solve) and gelsd both sit within ~eps * kappa of the exact
+    Jacobi SVD, preprocess.hip plane_solve) and gelsd both sit within ~eps * kappa of the exact
     (rank-truncated, minimum-norm) solution, kappa = s_1 / s_rank; ill-conditioned full-rank
     designs add the least-squares kappa^2 tan(theta) term (measured <= 51 eps kappa on
     ``stress_xy_line``, <= 4 elsewhere).  The contract: the same rank decision, every coefficient

@@ -986,6 +986,32 @@ def test_dbscan_fine_grid_vs_oracle(cuda, seed, eps, ms):
     assert np.array_equal(lab.cpu().numpy(), want)
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8192])
+def test_dbscan_scan_block_edge_vs_oracle(cuda, n):
+    """The rank scan covers n + 1 entries in blocks of 4 096 and stores the total at out[n]: n just
+    below, on and above one block, and on two.  Two blobs in a uniform background, the last n // 16
+    points exact duplicates of the first; seed n, eps 0.25, min_samples 5 take the fine grid, and the
+    oracle's answer was checked on the CPU for all four n: 24 to 67 clusters, 179 to 508 border
+    points, 585 to 672 noise points (asserted below as at least 2, 1 and 1)."""
+    import torch
+    from lidar_ai_recommendation_software_amd import _native as nat
+    rng = np.random.default_rng(n)
+    x = np.concatenate([rng.normal(0.0, 0.3, (n // 2, 3)), rng.normal(0.0, 0.3, (n // 4, 3)) + [4.0, 0.0, 0.0],
+                        rng.uniform([-1.5, -1.5, -1.0], [5.5, 1.5, 1.0], (n - n // 2 - n // 4, 3))])
+    x = rng.permutation(x)
+    x[-(n // 16):] = x[:n // 16]
+    want, wcnt = tier_r.dbscan_labels(x, 0.25, 5, return_counts=True)
+    assert want.max() >= 1 and np.any((wcnt < 5) & (want >= 0)) and np.any(want < 0)
+    xt = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    lab = torch.empty(n, dtype=torch.int64, device="cuda")
+    cnt = torch.empty(n, dtype=torch.int32, device="cuda")
+    nat.call("lidar_dbscan_f64", nat.handle(0), nat.ptr(xt), n, 0.25, 5, nat.ptr(lab), nat.ptr(cnt), nat.stream_ptr())
+    assert np.array_equal(cnt.cpu().numpy(), wcnt)
+    assert np.array_equal(lab.cpu().numpy(), want)
+    nat.call("lidar_dbscan_f64", nat.handle(0), nat.ptr(xt), n, 0.25, 5, nat.ptr(lab), None, nat.stream_ptr())
+    assert np.array_equal(lab.cpu().numpy(), want)
+
+
 def test_venue_grid_equals_grid_density_of_all_people(cuda):
     """people of many frames binned into one fixed venue grid equal
     calculate_grid_density of all those people over the venue extent, bit for bit."""
