@@ -445,6 +445,25 @@ int lidar_people_batch_f64(lidar_handle *h, const double *compact_xyz, const int
                            const int64_t *offsets, int32_t frames, int64_t max_n, const double *scalars,
                            double *people, int64_t *kdev, void *stream);
 
+/* People from per-point class labels (csrc/class_people.hip): xyz (batch, n, 3) fp32,
+ * labels (batch, n) int32 (a segmenter's output).  Per frame f, every frame independent and a batch equal
+ * to its frames one at a time, bit for bit: S_f = the indices i, ascending, with labels[f, i] == cls and
+ * three finite coordinates (a NaN or +-inf coordinate is never selected); nsel[f] = |S_f|.  The selected
+ * points, widened to fp64 in index order, get the labels of lidar_dbscan_f64(eps, min_samples) (sklearn
+ * DBSCAN).  instance (batch, n) int32: that label for a selected point, -1 for every other point (wrong
+ * class, non-finite, noise).  people (batch, cap, 2) fp64: row c of frame f = the (x, y) centroid of cluster
+ * c with lidar_people_f64's arithmetic (sequential index-order sums, one division); k[f] (int64) = the
+ * number of clusters; when k[f] > cap only the first cap rows are written (k[f] keeps the true count), and
+ * rows past min(k[f], cap) are not touched.  extent (batch, 4) fp64: x_min, x_max, y_min, y_max over ALL
+ * finite points of the frame, of every class; a frame without a finite point gets +inf, -inf, +inf, -inf
+ * and k = nsel = 0.  Asynchronous on `stream`: no host synchronisation, no host-staged parameter block;
+ * all outputs are device arrays.  Workspace: the handle's, sized for nsel = n in every frame.
+ * LIDAR_EINVAL: a null pointer, batch < 0 or > 65535, n < 1 or >= 2^31, eps not positive and finite,
+ * min_samples < 1, cap < 1.  batch == 0 returns LIDAR_OK. */
+int lidar_class_people_f32(lidar_handle *h, const float *xyz, const int32_t *labels, int64_t batch, int64_t n,
+                           int32_t cls, double eps, int32_t min_samples, int64_t cap, int32_t *instance,
+                           double *people, int64_t *k, int64_t *nsel, double *extent, void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

@@ -15,12 +15,6 @@ namespace {
 using namespace lidar::tier_r;
 
 // ------------------------------------------------------------------ DBSCAN
-// params (double) P: [0] n, [1] eps, [2..4] lo, [5..7] hi, [8] cell, [9..11] dims,
-// [12] ncell, [13] clusters, [14] active (n > 10 for the preprocess path), [15] stencil radius
-// R in cells (1 or 2), [16] same-cell shortcut (1: cells of side eps/sqrt(3), see dbscan_setup)
-enum : int { P_N = 0, P_EPS = 1, P_LO = 2, P_HI = 5, P_CELL = 8, P_DIM = 9, P_NCELL = 12,
-             P_NCLUST = 13, P_ACTIVE = 14, P_R = 15, P_INTRA = 16, P_COUNT = 20 };
-
 __global__ void dbscan_params_from_preprocess(const double *S_in, DbscanWs w, FrameMap fm)
 {
     if (threadIdx.x) return;
@@ -572,6 +566,12 @@ void dbscan_params_from_scalars(const double *scalars, const DbscanWs &w, hipStr
 void dbscan_nclust_to_scalars(const DbscanWs &w, double *scalars, hipStream_t s, FrameMap fm, int frames)
 {
     hipLaunchKernelGGL(nclust_kernel, dim3(1, frames), dim3(64), 0, s, w, scalars, fm);
+}
+
+int scan_u32(const DbscanWs &w, const uint32_t *src, uint32_t *dst, int idx, int64_t extra, int64_t nblk, hipStream_t s,
+             FrameMap fm, int frames)
+{
+    return run_scan(w, src, dst, idx, extra, nblk, s, fm, frames);
 }
 
 int run_dbscan(lidar_handle *h, int64_t nmax, int32_t min_samples, const DbscanWs &w, int64_t *labels, hipStream_t s,

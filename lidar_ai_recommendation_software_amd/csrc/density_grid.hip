@@ -265,6 +265,22 @@ __global__ __launch_bounds__(kT) void density_batch_kernel(const double *people_
 
 }  // namespace
 
+namespace lidar {
+namespace tier_r {
+
+int people_of_frames(lidar_handle *h, const double *xyz, const int64_t *labels, int64_t max_n, const int64_t *kdev,
+                     double *people, const double *scalars, hipStream_t s, FrameMap fm, int frames)
+{
+    lidar::Span sp(h, "people", s);
+    const unsigned pb = (unsigned)std::max(1, std::min(256, 2048 / std::max(1, frames)));
+    hipLaunchKernelGGL(people_kernel, dim3(pb, frames), dim3(kT), 0, s, xyz, labels, max_n, kdev, people, scalars, fm);
+    LAUNCH_CHECK();
+    return LIDAR_OK;
+}
+
+}  // namespace tier_r
+}  // namespace lidar
+
 // ====================================================================== C-ABI
 LIDAR_EXPORT int lidar_people_f64(lidar_handle *h, const double *xyz, const int64_t *labels, int64_t n,
                                   double *people, int64_t *k_host, void *stream)

@@ -1,6 +1,6 @@
 // tier_r.hpp — what two of preprocess.hip, dbscan.hip and density_grid.hip share: sizes, the scalars slots,
-// the frame map, fp64 rounding wrappers, workgroup min / max / scan, the DBSCAN workspace and dbscan.hip's
-// host entry points for preprocess.hip.  Kernels stay local to their translation unit.
+// the frame map, fp64 rounding wrappers, workgroup min / max / scan, the DBSCAN parameter block and workspace,
+// and the host entry points of dbscan.hip and density_grid.hip for preprocess.hip and class_people.hip.  Kernels stay local to their translation unit.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -112,6 +112,14 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t *wt
     return base + incl - v;
 }
 
+// ------------------------------------------------------------------ DBSCAN parameter block
+// params (double) P: [0] n, [1] eps, [2..4] lo, [5..7] hi, [8] cell, [9..11] dims,
+// [12] ncell, [13] clusters, [14] active (n > 10 for the preprocess path), [15] stencil radius
+// R in cells (1 or 2), [16] same-cell shortcut (1: cells of side eps/sqrt(3), see dbscan_setup),
+// [17] class_people.hip's point count of the whole frame (the length of its selection scan)
+enum : int { P_N = 0, P_EPS = 1, P_LO = 2, P_HI = 5, P_CELL = 8, P_DIM = 9, P_NCELL = 12,
+             P_NCLUST = 13, P_ACTIVE = 14, P_R = 15, P_INTRA = 16, P_NALL = 17, P_COUNT = 20 };
+
 // ------------------------------------------------------------------ DBSCAN workspace
 // One frame's DBSCAN buffers (carve_dbscan names, types and sizes them) and the points x they
 // cluster: the preprocess path's scaled cloud inside the same workspace, or the caller's own array
@@ -169,6 +177,16 @@ int run_dbscan(lidar_handle *h, int64_t nmax, int32_t min_samples, const DbscanW
                FrameMap fm, int frames, bool count_only = false, bool exact_counts = false);
 // every frame's cluster count, from P into its scalars
 void dbscan_nclust_to_scalars(const DbscanWs &w, double *scalars, hipStream_t s, FrameMap fm, int frames);
+// exclusive scan of every frame's P[idx] (+extra) entries of src into dst (dst[count] = the total), src
+// and dst unshifted pointers into the workspace; nblk: w.nblk_pts / w.nblk_cells, whichever bounds the count
+int scan_u32(const DbscanWs &w, const uint32_t *src, uint32_t *dst, int idx, int64_t extra, int64_t nblk, hipStream_t s,
+             FrameMap fm, int frames);
+
+// ---- density_grid.hip, for class_people.hip
+// people_kernel over `frames` frames: frame f's rows of xyz (3), labels (1) and people (2) start at row
+// fm.offs[f], its point count is scalars[f][S_NIN] (status slot 0), its cluster count kdev[f]
+int people_of_frames(lidar_handle *h, const double *xyz, const int64_t *labels, int64_t max_n, const int64_t *kdev,
+                     double *people, const double *scalars, hipStream_t s, FrameMap fm, int frames);
 
 }  // namespace tier_r
 }  // namespace lidar

@@ -819,6 +819,36 @@ def row_argmax(x, c, out=None, slot=0):
     return out
 
 
+def class_people(xyz, labels, cls, eps, min_samples=5, cap=None, slot=0):
+    """xyz (B, N, 3) float32, labels (B, N) int32 (segment()'s output), both contiguous on one CUDA device ->
+    (instance (B, N) int32, people (B, cap, 2) float64, k (B,) int64, nsel (B,) int64, extent (B, 4)
+    float64), device tensors, nothing synchronised.  Per frame: the points of class `cls` with finite
+    coordinates, widened to float64 in index order (nsel of them), clustered by DBSCAN(eps, min_samples)
+    exactly as lidar_dbscan_f64 / sklearn; instance: a selected point's cluster, -1 for every other point
+    (wrong class, non-finite, noise); people[f, :min(k[f], cap)]: the clusters' (x, y) centroids (np.mean of
+    the member rows), rows past that untouched; k: the cluster counts (also when above cap; cap defaults to
+    N); extent: x_min, x_max, y_min, y_max over all finite points of the frame (lidar_class_people_f32)."""
+    _dev_check(xyz, labels)
+    if xyz.dtype != torch.float32 or xyz.dim() != 3 or xyz.shape[2] != 3 or xyz.shape[1] < 1:
+        raise ValueError("class_people: xyz must be (B, N, 3) float32 with N >= 1")
+    B, N, _ = xyz.shape
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (B, N):
+        raise ValueError(f"class_people: labels must be ({B}, {N}) int32, got {labels.dtype} {tuple(labels.shape)}")
+    if labels.device != xyz.device:
+        raise ValueError("class_people: xyz and labels must be on the same device")
+    cap = N if cap is None else int(cap)
+    dev = xyz.device
+    instance = torch.empty((B, N), dtype=torch.int32, device=dev)
+    people = torch.empty((B, max(cap, 0), 2), dtype=torch.float64, device=dev)
+    k = torch.empty((B,), dtype=torch.int64, device=dev)
+    nsel = torch.empty((B,), dtype=torch.int64, device=dev)
+    extent = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    nat.call("lidar_class_people_f32", nat.handle(dev.index, slot), nat.ptr(xyz), nat.ptr(labels), B, N, int(cls),
+             float(eps), int(min_samples), cap, nat.ptr(instance), nat.ptr(people), nat.ptr(k), nat.ptr(nsel),
+             nat.ptr(extent), nat.stream_ptr())
+    return instance, people, k, nsel, extent
+
+
 # ----------------------------------------------------------------- decoder configuration and weights
 # Feature-propagation MLPs, deepest level first (one per encoder level), then the head's hidden layers;
 # the input widths follow from the encoder configuration (fp_input_widths), so it serves SSG and MSG.
@@ -1286,6 +1316,13 @@ class PointNet2Segmenter:
         logits = self.forward(xyz, max_bytes=max_bytes)
         B, N, nc = logits.shape
         return row_argmax(logits.view(B * N, nc), nc).view(B, N)
+
+    def people(self, xyz, person_class, eps, min_samples=5, metric_xyz=None):
+        """-> (labels, (instance, people, k, nsel, extent)): segment(xyz), then class_people of the points
+        labelled `person_class`.  The network sees xyz (normalised coordinates); the clustering runs on
+        metric_xyz (the same points in metres, (B, N, 3) float32) when given, else on xyz."""
+        labels = self.segment(xyz)
+        return labels, class_people(xyz if metric_xyz is None else metric_xyz, labels, person_class, eps, min_samples)
 
     __call__ = forward
 
