@@ -464,6 +464,44 @@ int lidar_class_people_f32(lidar_handle *h, const float *xyz, const int32_t *lab
                            int32_t cls, double eps, int32_t min_samples, int64_t cap, int32_t *instance,
                            double *people, int64_t *k, int64_t *nsel, double *extent, void *stream);
 
+/* Measured crowd flow (csrc/track.hip; DESIGN.md §3 "People tracking", §4.9): the people of T consecutive
+ * frames associated across every consecutive pair of frames, and their velocities accumulated on the venue
+ * grid.  All arithmetic fp64, one rounding per operation.  Both calls are asynchronous on `stream`: no host
+ * synchronisation, no host-staged parameter block, every array a device array; scratch is the handle's
+ * workspace.
+ *
+ * lidar_track_people_f64: people (frames, cap, 2) and k (frames) are lidar_class_people_f32's outputs;
+ * K_t = min(max(k[t], 0), cap), rows at or past K_t are never read for meaning.  Per pair (t-1, t)
+ * independently, A = the K_(t-1) rows of frame t-1, B = the K_t rows of frame t: d(i, j) = (dx*dx) + (dy*dy)
+ * with dx = B[j].x - A[i].x, dy = B[j].y - A[i].y; (i, j) is a candidate iff d <= gate*gate (inclusive,
+ * the fp64 product; a row with a NaN or infinite coordinate is never a candidate, in either role);
+ * fwd[i] = the candidate j with the smallest (d, j) in lexicographic order, bwd[j] = the candidate i with
+ * the smallest (d, i), -1 without a candidate; j is matched to i iff bwd[j] == i and fwd[i] == j (mutual
+ * nearest neighbour).  prev (frames, cap) int32: i for a matched row, -1 otherwise (unmatched, every row
+ * of frame 0, every row at or past K_t).  velocity (frames, cap, 2): ((B[j].x - A[i].x) / dt,
+ * (B[j].y - A[i].y) / dt) for a matched row, (0, 0) for every other (prev == -1 means "no measurement",
+ * not the zero).  track_id (frames, cap) int32: a row j < K_t with prev == -1 is a new detection, its id
+ * the number of new detections before it in (t, j) ascending order; a matched row takes
+ * track_id[t-1][prev[t][j]]; rows at or past K_t get -1.  ntracks (one int64): the number of new
+ * detections.  Every element of every output is written.
+ *
+ * lidar_flow_cells_f64: the grid is lidar_venue_counts_f64's (x0 = x_min - 2 grid, y0 = y_min - 2 grid,
+ * (nx, ny) = lidar_grid_dims; np.arange edges, searchsorted right, the last edge closed, outside dropped).
+ * Every matched detection (t >= 1, j < K_t, prev[t][j] >= 0) is binned by its own position people[t][j]:
+ * count (nx, ny) int32 = the matched detections per cell, vsum (nx, ny, 2) = the sum of their velocities
+ * added sequentially in (t, j) ascending order starting from 0.0.  Both are overwritten; a cell without a
+ * detection holds 0 and (0, 0).
+ *
+ * LIDAR_EINVAL: a null pointer, frames < 0 or > 65535, cap < 1, frames * cap >= 2^31, dt / gate / grid not
+ * positive and finite, x0 / y0 not finite, nx or ny < 1, nx * ny >= 2^31.  frames == 0 returns LIDAR_OK
+ * and writes nothing; frames == 1 is valid (no pairs: ids 0 .. K_0 - 1). */
+int lidar_track_people_f64(lidar_handle *h, const double *people, const int64_t *k, int64_t frames, int64_t cap,
+                           double dt, double gate, int32_t *prev, int32_t *track_id, double *velocity,
+                           int64_t *ntracks, void *stream);
+int lidar_flow_cells_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                         const double *velocity, int64_t frames, int64_t cap, double x0, double y0, double grid,
+                         int64_t nx, int64_t ny, int32_t *count, double *vsum, void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

@@ -45,16 +45,104 @@ class CrowdFlowModel:
         magnitudes = flow_vectors["magnitudes"]
         vectors = flow_vectors["vectors"]
         avg_speed = np.mean(magnitudes)
+        dominant_direction = self._dominant_direction(vectors)
+        bottlenecks = self._identify_bottlenecks(flow_vectors, processed_data)
+        return {"flow_vectors": flow_vectors, "avg_speed": avg_speed,
+                "dominant_direction": dominant_direction, "bottlenecks": bottlenecks}
+
+    def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
+                         min_observations=1):
+        """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
+
+        people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
+        or a list of T host arrays (K_t, 2) (``analyze_frames``' ``"people_positions"``).  dt: seconds between
+        frames; gate: the largest displacement accepted between two frames, metres (default max_speed * dt);
+        x_range / y_range: the venue's extent, whose ``VenueGrid`` grid the flow lives on.  People are
+        associated across frames by mutual nearest neighbour and every matched detection's velocity added into
+        the cell of its position (``people_tracking``; csrc/track.hip), with one read-back at the end.
+
+        Returns ``analyze``'s keys — flow_vectors (positions: the centres of the cells with at least
+        min_observations matched detections, y index outer and x index inner as the reference's meshgrid ravel;
+        vectors: the cells' mean velocity; magnitudes), avg_speed, dominant_direction, bottlenecks — and tracks
+        (identities seen), matched (detections with a measured velocity), observations (m,) int32 per position,
+        track_ids / velocities: per frame (K_t,) int32 and (K_t, 2) float64."""
+        import torch
+        from . import people_tracking as pt
+        from .global_density import venue_centres
+
+        def positive(name, v):
+            v = float(v)
+            if not (v > 0.0 and np.isfinite(v)):
+                raise ValueError(f"analyze_sequence: {name} must be positive and finite, got {v}")
+            return v
+
+        def extent(name, r):
+            r = tuple(float(v) for v in r)
+            if len(r) != 2 or not np.all(np.isfinite(r)) or r[0] > r[1]:
+                raise ValueError(f"analyze_sequence: {name} must be a finite (min, max) with min <= max, got {r}")
+            return r
+
+        dt = positive("dt", dt)
+        gate = positive("gate", float(max_speed) * dt if gate is None else gate)
+        grid_size = positive("grid_size", grid_size)
+        x_range, y_range = extent("x_range", x_range), extent("y_range", y_range)
+        if int(min_observations) != min_observations or min_observations < 1:
+            raise ValueError(f"analyze_sequence: min_observations must be an integer >= 1, got {min_observations}")
+        if isinstance(people, torch.Tensor):
+            if k is None:
+                raise ValueError("analyze_sequence: a people tensor needs k")
+        else:
+            if k is not None:
+                raise ValueError("analyze_sequence: k goes with a people tensor; a list carries its own counts")
+            rows = [np.asarray(p, dtype=np.float64) for p in people]
+            for t, p in enumerate(rows):
+                if p.ndim != 2 or p.shape[1] != 2:
+                    raise ValueError(f"analyze_sequence: frame {t} must be (K, 2), got {p.shape}")
+            packed = np.zeros((len(rows), max([1] + [len(p) for p in rows]), 2), dtype=np.float64)
+            for t, p in enumerate(rows):
+                packed[t, :len(p)] = p
+            people = torch.from_numpy(packed).cuda()
+            k = torch.tensor([len(p) for p in rows], dtype=torch.int64).to(people.device)
+
+        prev, track_id, velocity, ntracks = pt.track_people(people, k, dt, gate)
+        count, vsum, _ = pt.flow_cells(people, k, prev, velocity, x_range, y_range, grid_size)
+        host = [t.to("cpu", non_blocking=True) for t in (k, prev, track_id, velocity, ntracks, count, vsum)]
+        torch.cuda.current_stream(people.device).synchronize()  # the one read-back
+        kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host)
+        K = np.minimum(np.maximum(kh, 0), people.shape[1])
+        extras = {"tracks": int(ntracks), "matched": int(np.sum(prev >= 0)),
+                  "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
+                  "velocities": [velocity[t, :K[t]] for t in range(len(K))]}
+        if extras["matched"] == 0:
+            return {"flow_vectors": {"positions": np.zeros((0, 2)), "vectors": np.zeros((0, 2)),
+                                     "magnitudes": np.zeros(0)},
+                    "avg_speed": 0.0, "dominant_direction": "N/A", "bottlenecks": [],
+                    "observations": np.zeros(0, dtype=np.int32), **extras}
+        grid_x, grid_y = venue_centres(x_range, y_range, grid_size)  # VenueGrid.centres()
+        iy, ix = np.nonzero(count.T >= min_observations)  # y index outer, x index inner
+        observations = count[ix, iy]
+        vectors = vsum[ix, iy] / observations[:, None]
+        vx, vy = vectors[:, 0], vectors[:, 1]
+        flow_vectors = {"positions": np.column_stack([grid_x[ix], grid_y[iy]]).reshape(-1, 2), "vectors": vectors,
+                        "magnitudes": np.sqrt(vx * vx + vy * vy)}
+        if len(observations) == 0:  # matched, but no cell reaches min_observations
+            avg_speed = 0.0
+        else:
+            avg_speed = np.mean(flow_vectors["magnitudes"])
+        return {"flow_vectors": flow_vectors, "avg_speed": avg_speed,
+                "dominant_direction": self._dominant_direction(vectors),
+                "bottlenecks": self._identify_bottlenecks(flow_vectors, None),
+                "observations": observations.astype(np.int32), **extras}
+
+    @staticmethod
+    def _dominant_direction(vectors):
+        """``crowd_flow_model.py:66-79``: the compass octant of the mean vector."""
         if len(vectors) > 0:  # the reference's scalar epilogue, same numpy calls
             avg_vector = np.mean(vectors, axis=0)
             angle = np.arctan2(avg_vector[1], avg_vector[0]) * 180 / np.pi
             directions = ["E", "NE", "N", "NW", "W", "SW", "S", "SE", "E"]
-            dominant_direction = directions[int((angle + 22.5) % 360 / 45)]
-        else:
-            dominant_direction = "N/A"
-        bottlenecks = self._identify_bottlenecks(flow_vectors, processed_data)
-        return {"flow_vectors": flow_vectors, "avg_speed": avg_speed,
-                "dominant_direction": dominant_direction, "bottlenecks": bottlenecks}
+            return directions[int((angle + 22.5) % 360 / 45)]
+        return "N/A"
 
     def _generate_simulated_flow(self, people_positions, processed_data):
         """``crowd_flow_model.py:88-184``.  Seeds and draws the GLOBAL legacy NumPy RNG

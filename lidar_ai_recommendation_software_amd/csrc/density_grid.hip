@@ -511,21 +511,8 @@ LIDAR_EXPORT int lidar_cell_radius_density_f64(lidar_handle *h, const double *pe
 // edges np.arange(x0, ..., g) (e[0] = a, e[1] = a + g, e[i] = a + i * ((a + g) - a), numpy's
 // DOUBLE_fill), searchsorted right with the last edge closed, points outside dropped.  Counts
 // add into int32 cells, so the frames of a rank and then the ranks (one RCCL all-reduce) sum.
-__device__ __forceinline__ double arange_edge(double a, double g, int64_t i)
-{
-    return i == 0 ? a : (i == 1 ? dadd(a, g) : dadd(a, dmul((double)i, dsub(dadd(a, g), a))));
-}
-__device__ __forceinline__ int64_t arange_bin(double a, double g, int64_t nb, double v)
-{
-    int64_t lo = 0, hi = nb + 1;  // first edge index with e[idx] > v
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (arange_edge(a, g, mid) <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    if (v == arange_edge(a, g, nb)) --lo;  // the last edge is closed
-    return lo;                             // bin lo - 1 when 1 <= lo <= nb
-}
+// arange_edge / arange_bin: tier_r.hpp (shared with track.hip's flow cells)
+using lidar::tier_r::arange_bin;
 __global__ void venue_counts_kernel(const double *__restrict__ people, int64_t k, double x0, double y0, double g,
                                     int64_t nx, int64_t ny, int32_t *__restrict__ counts)
 {

@@ -1,5 +1,6 @@
 // tier_r.hpp — what two of preprocess.hip, dbscan.hip and density_grid.hip share: sizes, the scalars slots,
 // the frame map, fp64 rounding wrappers, workgroup min / max / scan, the DBSCAN parameter block and workspace,
+// the venue grid's binning (density_grid.hip, track.hip),
 // and the host entry points of dbscan.hip and density_grid.hip for preprocess.hip and class_people.hip.  Kernels stay local to their translation unit.
 #pragma once
 #include <algorithm>
@@ -52,6 +53,25 @@ __device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a,
 __device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
 __device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
 __device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
+
+// ---- the venue grid's binning (density_grid.hip's venue_counts_kernel, track.hip's cell_kernel):
+// calculate_grid_density's np.arange edges (e[0] = a, e[1] = a + g, e[i] = a + i * ((a + g) - a), numpy's
+// DOUBLE_fill), searchsorted right with the last edge closed
+__device__ __forceinline__ double arange_edge(double a, double g, int64_t i)
+{
+    return i == 0 ? a : (i == 1 ? dadd(a, g) : dadd(a, dmul((double)i, dsub(dadd(a, g), a))));
+}
+__device__ __forceinline__ int64_t arange_bin(double a, double g, int64_t nb, double v)
+{
+    int64_t lo = 0, hi = nb + 1;  // first edge index with e[idx] > v
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (arange_edge(a, g, mid) <= v) lo = mid + 1;
+        else hi = mid;
+    }
+    if (v == arange_edge(a, g, nb)) --lo;  // the last edge is closed
+    return lo;                             // bin lo - 1 when 1 <= lo <= nb
+}
 
 // ---- workgroup helpers (1024 threads)
 struct BlockScratch {

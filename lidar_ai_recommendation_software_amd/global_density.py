@@ -20,6 +20,22 @@ import torch.distributed as dist
 from . import _native as nat
 
 
+def venue_grid(x_range, y_range, grid_size=1.0):
+    """(x0, y0, nx, ny) of the grid calculate_grid_density builds for the extent (data_processing.py:305-313's
+    margin of two cells, lidar_grid_dims)."""
+    g = float(grid_size)
+    nx, ny = nat.grid_dims(float(x_range[0]), float(x_range[1]), float(y_range[0]), float(y_range[1]), g)
+    return float(x_range[0]) - g * 2.0, float(y_range[0]) - g * 2.0, nx, ny
+
+
+def venue_centres(x_range, y_range, grid_size=1.0):
+    """(grid_x, grid_y) cell centres of that grid, as calculate_grid_density returns them."""
+    g = float(grid_size)
+    xe = np.arange(float(x_range[0]) - g * 2.0, (float(x_range[1]) + g * 2.0) + g, g)
+    ye = np.arange(float(y_range[0]) - g * 2.0, (float(y_range[1]) + g * 2.0) + g, g)
+    return (xe[:-1] + xe[1:]) / 2, (ye[:-1] + ye[1:]) / 2
+
+
 class VenueGrid:
     def __init__(self, x_range, y_range, grid_size=1.0, device=None):
         """x_range / y_range: the venue's extent (the (min, max) a frame's dimensions would give);
@@ -27,10 +43,7 @@ class VenueGrid:
         self.x_range = (float(x_range[0]), float(x_range[1]))
         self.y_range = (float(y_range[0]), float(y_range[1]))
         self.grid_size = float(grid_size)
-        self.nx, self.ny = nat.grid_dims(self.x_range[0], self.x_range[1], self.y_range[0], self.y_range[1],
-                                         self.grid_size)
-        self.x0 = self.x_range[0] - self.grid_size * 2.0  # data_processing.py:305-309's margin
-        self.y0 = self.y_range[0] - self.grid_size * 2.0
+        self.x0, self.y0, self.nx, self.ny = venue_grid(self.x_range, self.y_range, self.grid_size)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.counts = torch.zeros((self.nx, self.ny), dtype=torch.int32, device=self.device)
 
@@ -71,6 +84,4 @@ class VenueGrid:
 
     def centres(self):
         """(grid_x, grid_y) cell centres, as calculate_grid_density returns them."""
-        xe = np.arange(self.x0, (self.x_range[1] + self.grid_size * 2.0) + self.grid_size, self.grid_size)
-        ye = np.arange(self.y0, (self.y_range[1] + self.grid_size * 2.0) + self.grid_size, self.grid_size)
-        return (xe[:-1] + xe[1:]) / 2, (ye[:-1] + ye[1:]) / 2
+        return venue_centres(self.x_range, self.y_range, self.grid_size)

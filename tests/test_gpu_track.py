@@ -1,0 +1,402 @@
+"""lidar_track_people_f64 / lidar_flow_cells_f64 / people_tracking / CrowdFlowModel.analyze_sequence on the GPU:
+every output equal (np.array_equal) to the host specification of tests/track_reference.py, whose planted
+sequences tests/test_track_cpu.py shows to hold ties, candidates at the gate, non-mutual pairs, duplicates,
+births and deaths."""
+import numpy as np
+import pytest
+
+import class_people_reference as cref
+import track_reference as ref
+
+torch = pytest.importorskip("torch")
+from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
+from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
+from lidar_ai_recommendation_software_amd import pointnet2 as pn  # noqa: E402
+from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+OUTPUTS = ("prev", "track_id", "velocity", "ntracks")
+
+
+def dev(cuda, a):
+    return torch.from_numpy(np.array(a)).to(cuda)
+
+
+def run(cuda, people, k, dt, gate):
+    out = pt.track_people(dev(cuda, people), dev(cuda, np.asarray(k, dtype=np.int64)), dt, gate)
+    return dict(zip(OUTPUTS, (t.cpu().numpy() for t in out)))
+
+
+def check(got, want, what=""):
+    """The four tracking outputs over the full (T, cap) arrays."""
+    assert got["prev"].dtype == np.int32 and got["track_id"].dtype == np.int32
+    assert got["velocity"].dtype == np.float64 and got["ntracks"].dtype == np.int64
+    for name in ("prev", "track_id"):
+        bad = np.argwhere(got[name] != want[name])
+        assert bad.size == 0, f"{what} {name}: {len(bad)} entries differ, first at {bad[:5].tolist()}"
+    assert got["velocity"].tobytes() == want["velocity"].tobytes(), f"{what} velocity"
+    assert int(got["ntracks"]) == want["ntracks"], f"{what} ntracks {int(got['ntracks'])} != {want['ntracks']}"
+
+
+@pytest.mark.parametrize("case,gate", ref.planted_cases(), ids=str)
+def test_vs_spec(cuda, case, gate):
+    people, k = ref.planted_sequence(*case)
+    check(run(cuda, people, k, ref.DT, gate), ref.planted_spec(*case, gate))
+
+
+def lattice_frames(counts, cap, seed, shift=1):
+    """Frames of counts[t] people: the first min(K_(t-1), K_t) rows of a frame are those of the frame before moved
+    by `shift` steps of 2^-3 m in x, the rest fresh nodes of a 0.5 m lattice in a band of their own per frame (so
+    every person is 2^-3 m from where it was and at least 0.5 m from everybody else); rows permuted per frame."""
+    rng = np.random.default_rng(seed)
+    side = 256
+    people = np.full((len(counts), cap, 2), ref.JUNK)
+    people[:, 1::2, 0] = np.nan
+    nodes = rng.permutation(side * side)
+    used, last = 0, np.empty((0, 2))
+    for t, K in enumerate(counts):
+        keep = last[:K] + np.array([shift * ref.STEP, 0.0])
+        fresh = nodes[used:used + K - len(keep)]
+        used += len(fresh)
+        cur = np.concatenate([keep, np.column_stack([fresh % side, fresh // side]) * 0.5 + np.array([0.0, 200.0 * t])])
+        cur = cur[rng.permutation(K)]
+        people[t, :K] = cur
+        last = cur
+    return people, np.array(counts, dtype=np.int64)
+
+
+def test_block_and_tile_edges(cuda):
+    """K_t on the block (256) and tile (2048) edges, empty frames beside full ones, in one call."""
+    counts = [0, 1, 2, 255, 256, 257, 2047, 2048, 2049, 0, 2049]
+    people, k = lattice_frames(counts, 2049, 11)
+    want = ref.track_spec(people, k, ref.DT, 0.25)
+    for t in range(1, len(counts)):  # a pair with an empty side matches nothing; every other pair continues all it can
+        assert int(np.sum(want["prev"][t] >= 0)) == min(counts[t - 1], counts[t])
+    check(run(cuda, people, k, ref.DT, 0.25), want)
+
+
+def test_k_above_cap_and_junk_rows(cuda):
+    case = ref.PLANTED[1]
+    people, k = ref.planted_sequence(*case)
+    cap = people.shape[1]
+    # k above cap on frames whose rows are all real: cut the arrays at the smallest K_t
+    cut = int(k.min())
+    p2 = np.ascontiguousarray(people[:, :cut])
+    k2 = k.copy()
+    assert np.all(k2 >= cut) and np.any(k2 > cut)
+    k2[0] = 1 << 40
+    want = ref.track_spec(p2, k2, ref.DT, 0.5)
+    assert np.all(want["track_id"] >= 0)
+    check(run(cuda, p2, k2, ref.DT, 0.5), want, "k > cap")
+    # negative k counts as 0
+    k3 = k.copy()
+    k3[2] = -5
+    want3 = ref.track_spec(people, k3, ref.DT, 0.5)
+    assert np.all(want3["prev"][2:4] == -1)
+    check(run(cuda, people, k3, ref.DT, 0.5), want3, "k < 0")
+    # other junk past K_t: the same bits out
+    a = run(cuda, people, k, ref.DT, 0.5)
+    other = people.copy()
+    for t in range(len(k)):
+        other[t, k[t]:] = other[t, 0]  # a live row's position, the likeliest junk to be matched by mistake
+    other[-1, k[-1]:] = -np.inf
+    b = run(cuda, other, k, ref.DT, 0.5)
+    for name in OUTPUTS:
+        assert a[name].tobytes() == b[name].tobytes(), name
+    check(a, ref.planted_spec(*case, 0.5))
+
+
+def test_non_finite_rows(cuda):
+    case, gate = ref.PLANTED[1], 0.5
+    people, k = ref.planted_sequence(*case)
+    clean = ref.planted_spec(*case, gate)
+    people = people.copy()
+    T = len(k)
+    hit = np.zeros(people.shape[:2], dtype=bool)
+    bad = [(np.nan, 0), (np.inf, 0), (-np.inf, 0), (np.nan, 1), (np.inf, 1), (-np.inf, 1)]
+    for t in range(T):
+        # rows that the clean sequence matches (as a row of frame t, or as the previous row of one of frame t + 1)
+        rows = np.flatnonzero(clean["prev"][t] >= 0)[:3].tolist() if t else []
+        if t + 1 < T:
+            nxt = clean["prev"][t + 1]
+            rows += [r for r in nxt[nxt >= 0][:3].tolist() if r not in rows]
+        assert len(rows) >= 3
+        for n, r in enumerate(rows):
+            v, c = bad[(n + t) % len(bad)]
+            people[t, r, c] = v
+            hit[t, r] = True
+    want = ref.track_spec(people, k, ref.DT, gate)
+    got = run(cuda, people, k, ref.DT, gate)
+    check(got, want)
+    assert np.all(got["prev"][hit] == -1)  # never matched as a row of frame t ...
+    for t in range(1, T):  # ... nor as the previous row
+        p = got["prev"][t]
+        assert not np.any(hit[t - 1][p[p >= 0]])
+    ids = got["track_id"][hit]
+    assert len(set(ids.tolist())) == len(ids) and np.all(ids >= 0)  # a fresh id every frame
+    # they reach no flow cell: the cells equal those of the sequence without them
+    xr, yr = ref.extent_of(people, k)
+    x0, y0, nx, ny, _, _ = ref.venue_grid(xr, yr, 1.0)
+    wc, wv = ref.flow_cells_spec(people, k, want["prev"], want["velocity"], x0, y0, 1.0, nx, ny)
+    pd, kd = dev(cuda, people), dev(cuda, k)
+    count, vsum, grid = pt.flow_cells(pd, kd, dev(cuda, got["prev"]), dev(cuda, got["velocity"]), xr, yr, 1.0)
+    assert grid == (x0, y0, nx, ny)
+    assert np.array_equal(count.cpu().numpy(), wc) and vsum.cpu().numpy().tobytes() == wv.tobytes()
+    assert wc.sum() == int(np.sum(want["prev"] >= 0)) < int(np.sum(clean["prev"] >= 0))
+    assert np.isfinite(vsum.cpu().numpy()).all()
+
+
+def call_track(people, k, frames, cap, dt, gate, prev, track_id, velocity, ntracks):
+    nat.call("lidar_track_people_f64", nat.handle(people.device.index), nat.ptr(people), nat.ptr(k), frames, cap, dt,
+             gate, nat.ptr(prev), nat.ptr(track_id), nat.ptr(velocity), nat.ptr(ntracks), nat.stream_ptr())
+
+
+def test_pairs_are_independent(cuda):
+    case, gate = ref.PLANTED[0], 0.25
+    people, k = ref.planted_sequence(*case)
+    full = run(cuda, people, k, ref.DT, gate)
+    for t in range(1, len(k)):
+        two = run(cuda, people[t - 1:t + 1], k[t - 1:t + 1], ref.DT, gate)
+        assert two["prev"][1].tobytes() == full["prev"][t].tobytes(), t
+        assert two["velocity"][1].tobytes() == full["velocity"][t].tobytes(), t
+    # one frame: ids 0 .. K_0 - 1
+    one = run(cuda, people[:1], k[:1], ref.DT, gate)
+    K0, cap = int(k[0]), people.shape[1]
+    assert int(one["ntracks"]) == K0
+    assert np.array_equal(one["track_id"][0], np.where(np.arange(cap) < K0, np.arange(cap), -1))
+    assert np.all(one["prev"] == -1) and np.all(one["velocity"] == 0.0)
+    # no frame: nothing is written
+    pd, kd = dev(cuda, people), dev(cuda, k)
+    prev = torch.full((2, cap), 77, dtype=torch.int32, device=cuda)
+    tid = torch.full((2, cap), 77, dtype=torch.int32, device=cuda)
+    vel = torch.full((2, cap, 2), 77.0, dtype=torch.float64, device=cuda)
+    nt = torch.full((), 77, dtype=torch.int64, device=cuda)
+    call_track(pd, kd, 0, cap, ref.DT, gate, prev, tid, vel, nt)
+    assert bool((prev == 77).all()) and bool((tid == 77).all()) and bool((vel == 77.0).all()) and int(nt) == 77
+    out = pt.track_people(pd[:0], kd[:0], ref.DT, gate)
+    assert tuple(out[0].shape) == (0, cap) and int(out[3]) == 0
+
+
+def test_reversal_inverts_matches(cuda):
+    for case, gate in ((ref.PLANTED[1], 0.25), (ref.PLANTED[2], 0.5)):
+        people, k = ref.planted_sequence(*case)
+        ab = run(cuda, people[:2], k[:2], ref.DT, gate)["prev"][1]
+        ba = run(cuda, people[1::-1], k[1::-1], ref.DT, gate)["prev"][1]
+        assert np.sum(ab >= 0) >= 0.5 * k[1]
+        j = np.flatnonzero(ab >= 0)
+        assert np.array_equal(ba[ab[j]], j)  # B's row j continues A's row i <=> A's row i continues B's row j
+        assert np.sum(ba >= 0) == len(j)
+
+
+def test_errors(cuda):
+    people, k = ref.planted_sequence(*ref.PLANTED[0])
+    pd, kd = dev(cuda, people), dev(cuda, k)
+    T, cap, _ = people.shape
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            pt.track_people(pd, kd, bad, 0.25)
+        with pytest.raises(ValueError):
+            pt.track_people(pd, kd, ref.DT, bad)
+    with pytest.raises(ValueError):
+        pt.track_people(pd.float(), kd, ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd, kd.int(), ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd, kd[:-1], ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd[:, :, :1].contiguous(), kd, ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd.transpose(0, 1), kd, ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd.cpu(), kd, ref.DT, 0.25)
+    with pytest.raises(ValueError):
+        pt.track_people(pd, kd.cpu(), ref.DT, 0.25)
+    outs = pt.track_people(pd, kd, ref.DT, 0.25)
+    # what the entry points themselves reject (tests/test_track_cpu.py shows that each returns before a launch)
+    for frames, c, dt, gate in ((-1, cap, ref.DT, 0.25), (65536, cap, ref.DT, 0.25), (T, 0, ref.DT, 0.25),
+                                (65535, 1 << 16, ref.DT, 0.25), (T, cap, 0.0, 0.25), (T, cap, ref.DT, float("nan"))):
+        with pytest.raises(nat.LidarError, match="lidar_track_people_f64"):
+            call_track(pd, kd, frames, c, dt, gate, *outs)
+    count = torch.zeros((4, 4), dtype=torch.int32, device=cuda)
+    vsum = torch.zeros((4, 4, 2), dtype=torch.float64, device=cuda)
+    for frames, c, g, nx, ny in ((-1, cap, 1.0, 4, 4), (65536, cap, 1.0, 4, 4), (T, 0, 1.0, 4, 4), (T, cap, 0.0, 4, 4),
+                                 (T, cap, float("inf"), 4, 4), (T, cap, 1.0, 0, 4), (T, cap, 1.0, 4, 0)):
+        with pytest.raises(nat.LidarError, match="lidar_flow_cells_f64"):
+            nat.call("lidar_flow_cells_f64", nat.handle(cuda.index), nat.ptr(pd), nat.ptr(kd), nat.ptr(outs[0]),
+                     nat.ptr(outs[2]), frames, c, 0.0, 0.0, g, nx, ny, nat.ptr(count), nat.ptr(vsum), nat.stream_ptr())
+    with pytest.raises(ValueError):
+        pt.flow_cells(pd, kd, outs[0].long(), outs[2], (0.0, 4.0), (0.0, 4.0))
+    with pytest.raises(ValueError):
+        pt.flow_cells(pd, kd, outs[0], outs[2][:, :, :1].contiguous(), (0.0, 4.0), (0.0, 4.0))
+    with pytest.raises(ValueError):
+        pt.flow_cells(pd, kd, outs[0], outs[2], (0.0, 4.0), (0.0, 4.0), grid_size=0.0)
+    check(run(cuda, people, k, ref.DT, 0.25), ref.planted_spec(*ref.PLANTED[0], 0.25), "after errors")
+
+
+# ------------------------------------------------------------------ flow cells
+def venue_counts(cuda, pts, x0, y0, g, nx, ny):
+    counts = torch.zeros((nx, ny), dtype=torch.int32, device=cuda)
+    p = dev(cuda, np.ascontiguousarray(pts))
+    nat.call("lidar_venue_counts_f64", nat.handle(cuda.index), nat.ptr(p), len(pts), x0, y0, g, nx, ny, nat.ptr(counts),
+             nat.stream_ptr())
+    return counts.cpu().numpy()
+
+
+@pytest.mark.parametrize("case,gate,grid", [(ref.PLANTED[0], 0.25, 1.0), (ref.PLANTED[1], 0.5, 0.375),
+                                            (ref.PLANTED[2], 0.5, 1.0), (ref.PLANTED[2], 0.25, 3.7)], ids=str)
+def test_flow_cells_vs_spec(cuda, case, gate, grid):
+    """A venue smaller than the scene (a lattice node exactly on an interior edge, on the closed last edge, and
+    detections outside), and the scene's own extent."""
+    people, k = ref.planted_sequence(*case)
+    s = ref.planted_spec(*case, gate)
+    pd, kd = dev(cuda, people), dev(cuda, k)
+    prev, vel = dev(cuda, s["prev"]), dev(cuda, s["velocity"])
+    rows = ref.matched_rows(k, s["prev"])
+    pts = np.array([people[t, j] for t, j in rows])
+    (xlo, xhi), (ylo, yhi) = ref.extent_of(people, k)
+    # the grid starts two cells below the range: this one starts 1 m and 0.5 m inside the scene
+    inner = ((xlo + 2 * grid + 1.0, xlo + 2 * grid + 1.0 + 0.3 * (xhi - xlo)),
+             (ylo + 2 * grid + 0.5, ylo + 2 * grid + 0.5 + 0.3 * (yhi - ylo)))
+    for xr, yr in (((xlo, xhi), (ylo, yhi)), inner):
+        x0, y0, nx, ny, _, _ = ref.venue_grid(xr, yr, grid)
+        wc, wv = ref.flow_cells_spec(people, k, s["prev"], s["velocity"], x0, y0, grid, nx, ny)
+        count, vsum, g4 = pt.flow_cells(pd, kd, prev, vel, xr, yr, grid)
+        assert g4 == (x0, y0, nx, ny) and tuple(count.shape) == (nx, ny) and tuple(vsum.shape) == (nx, ny, 2)
+        assert count.dtype == torch.int32 and vsum.dtype == torch.float64
+        assert np.array_equal(count.cpu().numpy(), wc)
+        assert vsum.cpu().numpy().tobytes() == wv.tobytes()
+        assert np.array_equal(wc, venue_counts(cuda, pts, x0, y0, grid, nx, ny))
+    # the second venue: edges hit, detections dropped
+    xe, ye = ref.arange_edges(x0, grid, nx), ref.arange_edges(y0, grid, ny)
+    assert 0 < wc.sum() < len(rows)
+    if grid in (1.0, 0.375):  # grids whose edges are lattice nodes
+        assert np.any(np.isin(pts[:, 0], xe[1:-1])) and np.any(np.isin(pts[:, 1], ye[1:-1]))
+
+
+def test_flow_cells_closed_last_edge_and_order(cuda):
+    """Hand-made: detections on the closed last edge and just outside, on an interior edge; and a cell whose sum
+    depends on the order of its terms."""
+    g, xr, yr = 1.0, (0.0, 2.0), (0.0, 1.0)
+    x0, y0, nx, ny, _, _ = ref.venue_grid(xr, yr, g)
+    xe, ye = ref.arange_edges(x0, g, nx), ref.arange_edges(y0, g, ny)
+    pts = [(xe[nx], 0.5), (np.nextafter(xe[nx], np.inf), 0.5), (xe[2], ye[ny]), (xe[0], ye[0]),
+           (np.nextafter(xe[0], -np.inf), 0.5), (0.5, 0.5), (0.5, 0.25), (0.5, 0.75), (0.25, 0.5)]
+    vels = [(1.0, 0.0)] * 5 + [(1e16, 1.0), (1.0, 1e-16), (-1e16, 1e-16), (1.0, -1.0)]
+    T, cap = 3, len(pts)
+    people = np.zeros((T, cap, 2))
+    people[1] = pts
+    people[2] = pts[::-1]
+    velocity = np.zeros((T, cap, 2))
+    velocity[1] = vels
+    velocity[2] = vels[::-1]
+    prev = np.full((T, cap), -1, dtype=np.int32)
+    prev[1:] = 0
+    prev[2, 2] = -1  # unmatched: not counted
+    k = np.array([cap, cap, cap + 7], dtype=np.int64)
+    wc, wv = ref.flow_cells_spec(people, k, prev, velocity, x0, y0, g, nx, ny)
+    assert wc[nx - 1].sum() >= 2 and wc.sum() == 2 * cap - 1 - 4  # two outside per frame
+    other = wv.copy()
+    cell = (ref.bin_right(xe, 0.5), ref.bin_right(ye, 0.5))
+    assert wc[cell] == 7 and wv[cell][0] != 4.0  # (1e16 + 1) - 1e16 + 1 ...: not the exact sum, so order shows
+    count, vsum, _ = pt.flow_cells(dev(cuda, people), dev(cuda, k), dev(cuda, prev), dev(cuda, velocity), xr, yr, g)
+    assert np.array_equal(count.cpu().numpy(), wc) and vsum.cpu().numpy().tobytes() == other.tobytes()
+
+
+# ------------------------------------------------------------------ the model
+def same_flow(got, want, what):
+    for key in ("positions", "vectors", "magnitudes"):
+        g, w = got["flow_vectors"][key], want["flow_vectors"][key]
+        assert g.dtype == np.float64 and g.shape == w.shape and g.tobytes() == w.tobytes(), f"{what}.{key}"
+    assert got["observations"].dtype == np.int32 and np.array_equal(got["observations"], want["observations"])
+    assert got["tracks"] == want["tracks"] and got["matched"] == want["matched"]
+    assert type(got["tracks"]) is int and type(got["matched"]) is int
+    for key in ("track_ids", "velocities"):
+        assert len(got[key]) == len(want[key])
+        for g, w in zip(got[key], want[key]):
+            assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), f"{what}.{key}"
+
+
+def test_analyze_sequence_constant_velocity(cuda):
+    n_side, T, dt = 6, 5, ref.STEP
+    n = n_side * n_side
+    gx, gy = np.meshgrid(np.arange(n_side, dtype=np.float64), np.arange(n_side, dtype=np.float64))
+    base = np.column_stack([gx.ravel(), gy.ravel()]) + 0.25
+    rng = np.random.default_rng(3)
+    frames = [(base + np.array([t * ref.STEP, 0.0]))[rng.permutation(n)] for t in range(T)]
+    model = CrowdFlowModel()
+    kw = dict(dt=dt, x_range=(0.0, float(n_side)), y_range=(0.0, float(n_side)))
+    a = model.analyze_sequence(frames, **kw)
+    people = np.full((T, n + 2, 2), np.nan)
+    people[:, :n] = np.stack(frames)
+    b = model.analyze_sequence(dev(cuda, people), dev(cuda, np.full(T, n, dtype=np.int64)), **kw)
+    for res in (a, b):
+        assert set(res) == {"flow_vectors", "avg_speed", "dominant_direction", "bottlenecks", "tracks", "matched",
+                            "observations", "track_ids", "velocities"}
+        assert res["tracks"] == n and res["matched"] == n * (T - 1)
+        assert np.all(res["flow_vectors"]["vectors"] == np.array([1.0, 0.0]))
+        assert np.all(res["flow_vectors"]["magnitudes"] == 1.0)
+        assert res["avg_speed"] == 1.0 and res["dominant_direction"] == "E"
+        assert res["observations"].sum() == n * (T - 1) and len(res["observations"]) == n
+        assert res["bottlenecks"] == []  # nothing is slower than 0.5 m/s
+        for t in range(T):
+            assert sorted(res["track_ids"][t].tolist()) == list(range(n))
+    same_flow(a, b, "list vs tensor")
+    # the positions: cell centres, y outer and x inner
+    pos = a["flow_vectors"]["positions"]
+    assert np.array_equal(pos[:n_side, 0], np.arange(n_side) + 0.5) and np.all(pos[:n_side, 1] == 0.5)
+    assert np.all(pos[n_side:2 * n_side, 1] == 1.5)
+
+
+@pytest.mark.parametrize("case,gate,grid,min_obs", [(ref.PLANTED[1], 0.5, 1.0, 1), (ref.PLANTED[1], 0.25, 1.0, 3),
+                                                    (ref.PLANTED[2], 0.5, 2.0, 1)], ids=str)
+def test_analyze_sequence_planted(cuda, case, gate, grid, min_obs):
+    people, k = ref.planted_sequence(*case)
+    xr, yr = ref.extent_of(people, k)
+    model = CrowdFlowModel()
+    got = model.analyze_sequence(dev(cuda, people), dev(cuda, k), dt=ref.DT, x_range=xr, y_range=yr, gate=gate,
+                                 grid_size=grid, min_observations=min_obs)
+    want = ref.sequence_result_spec(people, k, ref.DT, gate, xr, yr, grid, min_obs)
+    assert len(want["observations"]) >= 5 and want["observations"].min() >= min_obs
+    same_flow(got, want, "planted")
+    fv = want["flow_vectors"]
+    assert float(got["avg_speed"]).hex() == float(np.mean(fv["magnitudes"])).hex()
+    assert got["dominant_direction"] == CrowdFlowModel._dominant_direction(fv["vectors"])
+    assert got["bottlenecks"] == model._identify_bottlenecks(fv, None)
+    # gate defaults to max_speed * dt
+    again = model.analyze_sequence(dev(cuda, people), dev(cuda, k), dt=ref.DT, x_range=xr, y_range=yr,
+                                   max_speed=gate / ref.DT, grid_size=grid, min_observations=min_obs)
+    if np.float64(gate / ref.DT) * np.float64(ref.DT) == gate:
+        same_flow(again, want, "max_speed")
+
+
+def test_analyze_sequence_without_matches(cuda):
+    frames = [np.array([[0.0, 0.0], [1.0, 1.0]]), np.zeros((0, 2)), np.array([[3.0, 3.0]]), np.array([[0.0, 0.0]])]
+    res = CrowdFlowModel().analyze_sequence(frames, dt=0.1, x_range=(0.0, 3.0), y_range=(0.0, 3.0))
+    assert res["flow_vectors"]["positions"].shape == (0, 2) and res["flow_vectors"]["vectors"].shape == (0, 2)
+    assert res["flow_vectors"]["magnitudes"].shape == (0,)
+    assert res["avg_speed"] == 0.0 and res["dominant_direction"] == "N/A" and res["bottlenecks"] == []
+    assert res["tracks"] == 4 and res["matched"] == 0 and res["observations"].shape == (0,)
+    assert [len(v) for v in res["track_ids"]] == [2, 0, 1, 1] and [v.shape for v in res["velocities"]] == [
+        (2, 2), (0, 2), (1, 2), (1, 2)]
+    assert np.concatenate(res["track_ids"]).tolist() == [0, 1, 2, 3]
+
+
+def test_after_class_people(cuda):
+    """class_people's people and k go straight into track_people, device to device."""
+    xyz, labels = cref.planted_frames(1, 4096, 0)
+    T, eps = 4, 0.8
+    shifted = np.concatenate([xyz + np.array([t * ref.STEP, 0.0, 0.0], dtype=np.float32) for t in range(T)])
+    lab = np.repeat(labels, T, axis=0)
+    cap = 64
+    _, people, k, _, _ = pn.class_people(dev(cuda, shifted), dev(cuda, lab), cref.PERSON, eps, 5, cap=cap)
+    assert people.is_cuda and k.is_cuda
+    out = pt.track_people(people, k, ref.DT, 0.5)
+    ph, kh = people.cpu().numpy(), k.cpu().numpy()
+    assert np.all(kh >= 3)
+    # rows past k hold whatever was there: the specification must not depend on them either
+    ph = np.where(np.arange(cap)[None, :, None] < np.minimum(kh, cap)[:, None, None], ph, np.nan)
+    want = ref.track_spec(ph, kh, ref.DT, 0.5)
+    got = dict(zip(OUTPUTS, (t.cpu().numpy() for t in out)))
+    check(got, want)
+    assert int(np.sum(want["prev"] >= 0)) >= 3 * (T - 1)  # the clusters move with their frame
