@@ -16,6 +16,11 @@
 // The scale keeps the group's maximum below 2^14 (fp16 holds up to 65504), so no value can
 // overflow; elements below 2^-14 of the maximum keep an absolute precision of 2^-38 of it.  A NaN
 // or inf sets its own group's scale (its fp32 products would be NaN / inf anyway).
+// Layer 3 of the SA kernels (and every h3 plane of group_all's chain) is the exception to "maximum": its
+// group is still the 16-row tile (the row), but the scale is the BOUND colsum|W2| 2^e2 + max|b2| (bound_exp3,
+// out_bound_exp), not the tile's largest y2, so "within 2^14 of the maximum" reads "within 2^14 of that
+// bound": one huge |b2|, or cancelling W2 columns, lifts it above the data and the small y2 lose their lo
+// piece (measured envelope: INTEGRATION.md "Weights outside the h3 envelope"; tests/h3_model.py models it).
 //
 // Non-finite operands: an inf splits into hi = inf, lo = inf - inf = NaN, and a 0 piece times an
 // inf one is NaN, so every output an inf or NaN operand reaches is NaN in h3 where fp32 would give

@@ -19,6 +19,7 @@ per level; PointNet2Segmenter adds a per-point head and argmax.
 Layouts: xyz (B, N, 3) float32; features channels-last (B, N, C) float32.
 """
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -299,6 +300,13 @@ def _pack_branch(kind, layers, xyz_level=None):
     size, pack, dtype = _PACKERS[kind]
     (w1, _), (w2, _), (w3, _) = layers
     dims = ([] if kind == "x1" else [int(xyz_level)]) + [w1.shape[1], w2.shape[1], w3.shape[1]]
+    if kind == "x3":
+        spread, outlier = h3_envelope(layers)
+        if spread > H3_SPREAD_LOG2_MAX or outlier > H3_BIAS_OUTLIER_LOG2_MAX:
+            warnings.warn(f"SA branch weights outside the h3 kernels' measured 1e-4 envelope: channel spread 2^{spread:.1f} "
+                          f"(limit 2^{H3_SPREAD_LOG2_MAX:g}), |b2| outlier 2^{outlier:.1f} (limit "
+                          f"2^{H3_BIAS_OUTLIER_LOG2_MAX:g}); results stay within the h3 forward bound but small features "
+                          "may miss 1e-4: use x3=False (native fp32) for such weights", RuntimeWarning, stacklevel=3)
     lib = nat.load_library()
     out = np.zeros(getattr(lib, size)(*dims), dtype=dtype)
     arrs = [np.ascontiguousarray(a, dtype=np.float32) for layer in layers for a in layer]
@@ -332,9 +340,37 @@ def group_mlp16(p, q, idx, n, packed, widths, out, out_offset=0, xyz_level=False
     return out
 
 
+# The weights inside which the h3 SA kernels were measured to hold the 1e-4 contract (INTEGRATION.md "Weights
+# outside the h3 envelope"; tests/test_gpu_sa_precision.py): h3 scales a layer's weights by ONE power of two and
+# layer 3's input by a bound fed by max |b2|, so a channel far below its layer's maximum, or one huge |b2|,
+# costs the small values their low piece.  log2 thresholds of h3_envelope()'s two figures.
+H3_SPREAD_LOG2_MAX = 10.0   # held at 2^9.6 (per-channel scales spread over 2^8 in both layers), lost by 2^16.4
+H3_BIAS_OUTLIER_LOG2_MAX = 17.0  # held with one |b2| 2^16.6 above the median (layer 3's scale 2^15 above the data), lost by 2^24.6
+
+
+def h3_envelope(layers):
+    """(channel spread, bias outlier), log2, of a branch's [(W, b)] x 3 for the h3 kernels.  Channel spread:
+    over W2 and W3, how far the smallest input-row or output-column maximum lies below the layer's maximum
+    (all-zero rows and columns aside).  Bias outlier: max |b2| over the median |b2| (over the median column
+    maximum of |W2| when that median is zero): what lifts layer 3's scale above its data."""
+    spread = 0.0
+    for W, _ in layers[1:]:
+        A = np.abs(np.asarray(W, np.float64))
+        for axis in (0, 1):
+            m = A.max(axis=axis)
+            m = m[m > 0]
+            if m.size:
+                spread = max(spread, float(np.log2(A.max() / m.min())))
+    W2, b2 = (np.abs(np.asarray(a, np.float64)) for a in layers[1])
+    ref = np.median(b2) if np.median(b2) > 0 else np.median(W2.max(axis=0))
+    outlier = float(np.log2(b2.max() / ref)) if b2.max() > 0 and ref > 0 else 0.0
+    return spread, outlier
+
+
 def pack_branch_x3(layers, xyz_level):
     """Host-side packed image (uint8) for lidar_sa_group_mlp_x3_f32 (fp16 hi/lo fragments of each layer's
-    W 2^s, h3 arithmetic; csrc/h3.hpp)."""
+    W 2^s, h3 arithmetic; csrc/h3.hpp).  Warns (RuntimeWarning) for weights outside the envelope in which
+    the h3 kernels hold the 1e-4 contract (h3_envelope; PointNet2Backbone(x3=False) is the strict-fp32 path)."""
     return _pack_branch("x3", layers, xyz_level)
 
 
