@@ -502,6 +502,50 @@ int lidar_flow_cells_f64(lidar_handle *h, const double *people, const int64_t *k
                          const double *velocity, int64_t frames, int64_t cap, double x0, double y0, double grid,
                          int64_t nx, int64_t ny, int32_t *count, double *vsum, void *stream);
 
+/* Continuous people tracking (csrc/track.hip; DESIGN.md §3 "Continuous people tracking", §4.10): the
+ * association of lidar_track_people_f64 carried across calls and stitched over missed frames.  Asynchronous
+ * like its siblings: no host synchronisation, no host-staged parameter block, the id base read from device
+ * memory, scratch from the handle's workspace.
+ *
+ * lidar_track_stream_f64: people, k, frames, cap, dt, gate as lidar_track_people_f64.  max_gap = M: the
+ * number of consecutive frames a person may go undetected, 0 .. 7.  carry = C: the number of leading frames
+ * whose association state is given, 0 .. min(M + 1, frames).  State per detection (t, j), j < K_t: prev
+ * (frames, cap) int32, the predecessor's row or -1; gap (frames, cap) int32, the predecessor lives in frame
+ * t - gap (0 iff prev == -1); succ (frames, cap) uint8, 1 iff a later detection has this one as its
+ * predecessor; velocity (frames, cap, 2); track_id (frames, cap) int32.  The first C frames of all five are
+ * inputs and stay as they are, except that succ may go from 0 to 1; every element of the other frames is
+ * written (rows at or past K_t: prev -1, gap 0, succ 0, velocity (0, 0), track_id -1).
+ * Passes g = 1 .. M + 1 in ascending order; pass g, for every start frame u with max(C, g) <= u < frames and
+ * t = u - g, independently: A = the rows i < K_t of frame t with succ == 0, B = the rows j < K_u of frame u
+ * with prev == -1, both as the passes before left them; (i, j) is a candidate iff d(i, j) <= (gate*g)*(gate*g)
+ * (d as lidar_track_people_f64; gate*g, then its square, one fp64 product each); fwd, bwd and the mutual
+ * test as there, over A and B alone, ties to the lowest row index.  A matched pair: prev[u][j] = i,
+ * gap[u][j] = g, succ[t][i] = 1, velocity[u][j] = ((B.x - A.x) / (dt*g), (B.y - A.y) / (dt*g)), dt*g one fp64
+ * product.  Ids, for (u, j) ascending, u >= C, j < K_u: a row with prev == -1 takes *ntracks (as it came in)
+ * plus the number of such rows before it; a matched row takes track_id[u - gap][prev]; on return *ntracks
+ * (one device int64) has grown by the number of new detections.  With M = 0 and C = 0 and *ntracks = 0 the
+ * outputs are lidar_track_people_f64's bit for bit.  A sequence cut at any frame, the second call handed the
+ * last min(M + 1, cut) frames of the first (people, k, the five arrays, *ntracks left in place) as its
+ * carry, gives the frames from the cut on exactly what one call over the whole sequence gives.
+ *
+ * lidar_flow_cells_acc_f64: lidar_flow_cells_f64 over the detections of the frames t >= first only (a row
+ * of frame 0 with prev >= 0 is legitimate once there is a carry: only prev >= 0 and the row's own velocity
+ * are read); accumulate = 0 overwrites count and vsum, accumulate = 1 continues from them, every cell's
+ * sequential sum starting from the stored value, so that the calls of a stream add up to the bits of one
+ * call over the whole sequence.  lidar_flow_cells_f64 is first = 1, accumulate = 0.
+ *
+ * LIDAR_EINVAL: as lidar_track_people_f64 / lidar_flow_cells_f64, and max_gap outside 0 .. 7, carry outside
+ * 0 .. min(max_gap + 1, frames), first outside 0 .. frames, accumulate not 0 or 1.  frames == 0 returns
+ * LIDAR_OK and writes nothing; frames == carry is valid for lidar_track_stream_f64: nothing to link,
+ * nothing written, *ntracks unchanged. */
+int lidar_track_stream_f64(lidar_handle *h, const double *people, const int64_t *k, int64_t frames, int64_t cap,
+                           int64_t carry, double dt, double gate, int32_t max_gap, int32_t *prev, int32_t *gap,
+                           uint8_t *succ, double *velocity, int32_t *track_id, int64_t *ntracks, void *stream);
+int lidar_flow_cells_acc_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                             const double *velocity, int64_t frames, int64_t cap, int64_t first,
+                             int32_t accumulate, double x0, double y0, double grid, int64_t nx, int64_t ny,
+                             int32_t *count, double *vsum, void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

@@ -51,7 +51,7 @@ class CrowdFlowModel:
                 "dominant_direction": dominant_direction, "bottlenecks": bottlenecks}
 
     def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
-                         min_observations=1):
+                         min_observations=1, max_gap=0):
         """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
 
         people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
@@ -65,10 +65,15 @@ class CrowdFlowModel:
         min_observations matched detections, y index outer and x index inner as the reference's meshgrid ravel;
         vectors: the cells' mean velocity; magnitudes), avg_speed, dominant_direction, bottlenecks — and tracks
         (identities seen), matched (detections with a measured velocity), observations (m,) int32 per position,
-        track_ids / velocities: per frame (K_t,) int32 and (K_t, 2) float64."""
+        track_ids / velocities: per frame (K_t,) int32 and (K_t, 2) float64.
+
+        max_gap > 0 (at most 7) stitches a track over that many consecutive frames without a detection
+        (``people_tracking.track_stream``, DESIGN.md §3 "Continuous people tracking"): a detection is also
+        associated with the open detections up to max_gap + 1 frames back, and its velocity is the displacement
+        over that many dt.  The result then also holds gaps: per frame (K_t,) int32, the frame distance to each
+        row's predecessor (0: none)."""
         import torch
         from . import people_tracking as pt
-        from .global_density import venue_centres
 
         def positive(name, v):
             v = float(v)
@@ -88,6 +93,8 @@ class CrowdFlowModel:
         x_range, y_range = extent("x_range", x_range), extent("y_range", y_range)
         if int(min_observations) != min_observations or min_observations < 1:
             raise ValueError(f"analyze_sequence: min_observations must be an integer >= 1, got {min_observations}")
+        if int(max_gap) != max_gap or not 0 <= max_gap <= pt.MAX_GAP:
+            raise ValueError(f"analyze_sequence: max_gap must be an integer in 0 .. {pt.MAX_GAP}, got {max_gap}")
         if isinstance(people, torch.Tensor):
             if k is None:
                 raise ValueError("analyze_sequence: a people tensor needs k")
@@ -104,15 +111,57 @@ class CrowdFlowModel:
             people = torch.from_numpy(packed).cuda()
             k = torch.tensor([len(p) for p in rows], dtype=torch.int64).to(people.device)
 
-        prev, track_id, velocity, ntracks = pt.track_people(people, k, dt, gate)
+        if max_gap == 0:
+            prev, track_id, velocity, ntracks = pt.track_people(people, k, dt, gate)
+            gap = None
+        else:
+            prev, gap, _, velocity, track_id, ntracks = pt.track_stream(people, k, dt, gate, max_gap)
         count, vsum, _ = pt.flow_cells(people, k, prev, velocity, x_range, y_range, grid_size)
-        host = [t.to("cpu", non_blocking=True) for t in (k, prev, track_id, velocity, ntracks, count, vsum)]
+        dev = [k, prev, track_id, velocity, ntracks, count, vsum] + ([] if gap is None else [gap])
+        host = [t.to("cpu", non_blocking=True) for t in dev]
         torch.cuda.current_stream(people.device).synchronize()  # the one read-back
-        kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host)
+        kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host[:7])
         K = np.minimum(np.maximum(kh, 0), people.shape[1])
         extras = {"tracks": int(ntracks), "matched": int(np.sum(prev >= 0)),
                   "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
                   "velocities": [velocity[t, :K[t]] for t in range(len(K))]}
+        if gap is not None:
+            gap = host[7].numpy()
+            extras["gaps"] = [gap[t, :K[t]] for t in range(len(K))]
+        return self._measured_flow(count, vsum, x_range, y_range, grid_size, min_observations, extras)
+
+    def analyze_stream(self, tracker, min_observations=1):
+        """Measured flow of everything pushed into a ``people_tracking.PeopleTracker`` that was given a venue
+        extent: ``analyze_sequence``'s keys (``gaps`` included) from the tracker's accumulated cells, with one
+        read-back.  tracks / matched count the whole stream; track_ids / velocities / gaps are per frame for
+        the frames the tracker still holds, its last min(max_gap + 1, frames) ones (the rows of earlier frames
+        were returned by ``push``)."""
+        import torch
+
+        if int(min_observations) != min_observations or min_observations < 1:
+            raise ValueError(f"analyze_stream: min_observations must be an integer >= 1, got {min_observations}")
+        if tracker.grid is None:
+            raise ValueError("analyze_stream: the tracker was built without x_range / y_range: it holds no flow cells")
+        if tracker.frames == 0:
+            extras = {"tracks": 0, "matched": 0, "track_ids": [], "velocities": [], "gaps": []}
+            return self._measured_flow(None, None, None, None, None, min_observations, extras)
+        _, k, _, gap, _, velocity, track_id = tracker._carry
+        dev = (k, gap, velocity, track_id, tracker.ntracks, tracker.matched, tracker.count, tracker.vsum)
+        host = [t.to("cpu", non_blocking=True) for t in dev]
+        torch.cuda.current_stream(k.device).synchronize()  # the one read-back
+        kh, gap, velocity, track_id, ntracks, matched, count, vsum = (t.numpy() for t in host)
+        K = np.minimum(np.maximum(kh, 0), tracker.cap)
+        extras = {"tracks": int(ntracks), "matched": int(matched),
+                  "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
+                  "velocities": [velocity[t, :K[t]] for t in range(len(K))],
+                  "gaps": [gap[t, :K[t]] for t in range(len(K))]}
+        return self._measured_flow(count, vsum, tracker.x_range, tracker.y_range, tracker.grid_size, min_observations,
+                                   extras)
+
+    def _measured_flow(self, count, vsum, x_range, y_range, grid_size, min_observations, extras):
+        """analyze's keys from the flow cells (count, vsum) on the host."""
+        from .global_density import venue_centres
+
         if extras["matched"] == 0:
             return {"flow_vectors": {"positions": np.zeros((0, 2)), "vectors": np.zeros((0, 2)),
                                      "magnitudes": np.zeros(0)},

@@ -1,0 +1,180 @@
+"""CPU side of continuous people tracking: the two properties of the specification (tests/track_stream_reference.py)
+that the design rests on — max_gap = 0 without a carry is track_spec, and a stream cut anywhere equals the whole —
+the conditions on the gappy sequences that keep the GPU tests from passing vacuously, and the argument checks of
+the two entry points that return before the device is touched (no GPU needed)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import track_reference as ref
+import track_stream_reference as sref
+
+
+def same_state(a, b, what=""):
+    for name in sref.STATE:
+        assert a[name].dtype == b[name].dtype and a[name].tobytes() == b[name].tobytes(), f"{what} {name}"
+    assert a["ntracks"] == b["ntracks"], what
+
+
+@pytest.mark.parametrize("case,gate", ref.planted_cases(), ids=str)
+def test_max_gap_0_is_track_spec(case, gate):
+    people, k = ref.planted_sequence(*case)
+    want = ref.planted_spec(*case, gate)
+    got = sref.stream_spec(people, k, ref.DT, gate, 0)
+    for name in ("prev", "track_id", "velocity"):
+        assert got[name].dtype == want[name].dtype and got[name].tobytes() == want[name].tobytes(), name
+    assert got["ntracks"] == want["ntracks"]
+    assert np.array_equal(got["gap"], (want["prev"] >= 0).astype(np.int32))
+    # succ: exactly the rows some row of the next frame continues
+    succ = np.zeros_like(got["succ"])
+    for t in range(1, case[0]):
+        p = want["prev"][t]
+        succ[t - 1, p[p >= 0]] = 1
+    assert np.array_equal(got["succ"], succ)
+
+
+@pytest.mark.parametrize("case", sref.GAPPY, ids=str)
+@pytest.mark.parametrize("max_gap", [1, 2])
+def test_any_split_equals_the_whole(case, max_gap):
+    people, k = sref.gappy_sequence(*case)
+    T = case[0]
+    for gate in sref.GATES:
+        whole = sref.gappy_spec(*case, gate, max_gap)
+        for cut in range(T + 1):
+            same_state(sref.split_spec(people, k, ref.DT, gate, max_gap, [cut]), whole, f"gate {gate} cut {cut}")
+    # several cuts, an empty piece among them, pieces shorter than max_gap + 1
+    gate = sref.GATES[0]
+    whole = sref.gappy_spec(*case, gate, max_gap)
+    same_state(sref.split_spec(people, k, ref.DT, gate, max_gap, list(range(1, T))), whole, "every frame")
+    same_state(sref.split_spec(people, k, ref.DT, gate, max_gap, [1, 1, 3]), whole, "1, 0, 2, rest")
+
+
+@pytest.mark.parametrize("case", sref.GAPPY, ids=str)
+@pytest.mark.parametrize("gate", sref.GATES)
+@pytest.mark.parametrize("max_gap", [1, 2])
+def test_gappy_sequences_are_stitched(case, gate, max_gap):
+    """Conditions on the inputs of the GPU tests: a real share of the matched rows has gap >= 2, and the state is
+    consistent."""
+    people, k = sref.gappy_sequence(*case)
+    s = sref.gappy_spec(*case, gate, max_gap)
+    T, cap, _ = people.shape
+    K = ref.clamp_k(k, cap)
+    matched = int(np.sum(s["prev"] >= 0))
+    stitched = int(np.sum(s["gap"] >= 2))
+    print(f"{case} gate {gate} max_gap {max_gap}: {stitched} of {matched} matched rows stitched")
+    assert stitched >= 0.05 * matched, f"{stitched} of {matched}"
+    assert np.array_equal(s["gap"] > 0, s["prev"] >= 0) and s["gap"].max() <= max_gap + 1
+    assert int(s["succ"].sum()) == matched  # every matched row closes exactly one end
+    for t in range(T):
+        assert np.all(s["prev"][t, K[t]:] == -1) and np.all(s["track_id"][t, K[t]:] == -1)
+        assert len(set(s["track_id"][t, :K[t]].tolist())) == K[t]  # a track holds one row per frame at most
+        for j in np.flatnonzero(s["prev"][t] >= 0):
+            src = (t - s["gap"][t, j], s["prev"][t, j])
+            assert s["succ"][src] == 1 and s["track_id"][src] == s["track_id"][t, j]
+    ids = np.concatenate([s["track_id"][t, :K[t]] for t in range(T)])
+    assert set(ids.tolist()) == set(range(s["ntracks"]))
+    # stitching merges tracks: fewer identities than the pairwise tracker counts, and no fewer matches
+    base = sref.gappy_spec(*case, gate, 0)
+    assert s["ntracks"] < base["ntracks"] and matched > int(np.sum(base["prev"] >= 0))
+    assert s["ntracks"] == int(K.sum()) - matched
+
+
+def test_spec_on_a_hand_made_gap():
+    """An end with a candidate at gap 2 and another at gap 3: the smaller gap wins.  A tie at gap 2: the lowest row.
+    A candidate exactly at gate * 2: inclusive."""
+    nan = np.nan
+    people = np.full((4, 4, 2), nan)
+    # frame 0: a at (0, 0), b at (10, 0), c at (20, 0); frame 1: nobody
+    people[0, :3] = [(0.0, 0.0), (10.0, 0.0), (20.0, 0.0)]
+    # frame 2: a row 0.75 from a (inside gate * 2); two rows 0.5 from b on either side (a tie: row 1 wins)
+    people[2, :3] = [(0.75, 0.0), (10.5, 0.0), (9.5, 0.0)]
+    # frame 3: a row on a's very position (gap 3, distance 0; 0.75 > gate from frame 2's row 0), and one 1.0 from c
+    people[3, :2] = [(0.0, 0.0), (21.0, 0.0)]
+    k = np.array([3, 0, 3, 2])
+    s = sref.stream_spec(people, k, 0.5, 0.5, max_gap=2)
+    assert s["prev"][2].tolist() == [0, 1, -1, -1] and s["gap"][2].tolist() == [2, 2, 0, 0]
+    assert s["velocity"][2, 0].tolist() == [0.75, 0.0] and s["velocity"][2, 1].tolist() == [0.5, 0.0]
+    # a's end was closed at gap 2: the nearer row of frame 3 starts a new track; c is continued at gap 3 (1.0 <= 1.5)
+    assert s["prev"][3].tolist() == [-1, 2, -1, -1] and s["gap"][3].tolist() == [0, 3, 0, 0]
+    assert s["velocity"][3, 1].tolist() == [1.0 / 1.5, 0.0]
+    assert s["succ"][0].tolist() == [1, 1, 1, 0] and not s["succ"][1:].any()
+    assert s["track_id"][2].tolist() == [0, 1, 3, -1] and s["track_id"][3].tolist() == [4, 2, -1, -1]
+    assert s["ntracks"] == 5
+    # exactly at the gate of pass 2 (1.0 = 0.5 * 2) and one ulp past it
+    for x, hit in ((11.0, True), (np.nextafter(11.0, 12.0), False)):
+        p = np.full((3, 2, 2), nan)
+        p[0, 0], p[2, 0] = (10.0, 0.0), (x, 0.0)
+        s = sref.stream_spec(p, [1, 0, 1], 0.5, 0.5, max_gap=1)
+        assert (s["prev"][2, 0] == 0) == hit and s["ntracks"] == (1 if hit else 2)
+
+
+def test_dropout_scene_is_what_it_says():
+    for max_gap in (1, 2):
+        people, k, present, rows = sref.dropout_scene(5, 9, max_gap, 0.25, 5)
+        assert present[0].all() and present[-1].all() and not present.all(axis=0).any()
+        runs = [np.diff(np.flatnonzero(present[:, w])).max() - 1 for w in range(present.shape[1])]
+        assert max(runs) == max_gap and min(runs) >= 1
+        live = people[0, :k[0]]
+        d = np.sqrt(((live[:, None] - live[None]) ** 2).sum(-1))
+        assert d[d > 0].min() >= 4 * 0.25 * (max_gap + 1)
+
+
+def test_entry_points_reject_bad_arguments_before_any_launch():
+    from lidar_ai_recommendation_software_amd import _native as nat
+    lib = nat.load_library()
+    n = None
+    assert lib.lidar_track_stream_f64(n, n, n, 1, 1, 0, 0.1, 0.3, 0, n, n, n, n, n, n, n) == -1
+    assert lib.lidar_last_error().startswith(b"lidar_track_stream_f64: null pointer")
+    assert lib.lidar_flow_cells_acc_f64(n, n, n, n, n, 1, 1, 0, 0, 0.0, 0.0, 1.0, 1, 1, n, n, n) == -1
+    assert lib.lidar_last_error().startswith(b"lidar_flow_cells_acc_f64: null pointer")
+    # the checks come before the handle is touched: a call that passed them would crash on this dummy handle
+    p = ctypes.c_void_p(64)
+    T, cap, dt, gate = 7, 43, 0.1, 0.25
+    bad = [(-1, cap, 0, dt, gate, 0), (65536, cap, 0, dt, gate, 0), (T, 0, 0, dt, gate, 0),
+           (65535, 1 << 16, 0, dt, gate, 0), (2, 1 << 31, 0, dt, gate, 0), (T, cap, 0, 0.0, gate, 0),
+           (T, cap, 0, float("inf"), gate, 0), (T, cap, 0, dt, float("nan"), 0), (T, cap, 0, dt, -1.0, 0),
+           (T, cap, 0, dt, gate, -1), (T, cap, 0, dt, gate, 8), (T, cap, -1, dt, gate, 2), (T, cap, 2, dt, gate, 0),
+           (T, cap, 4, dt, gate, 2), (2, cap, 3, dt, gate, 7)]
+    for frames, c, carry, d, g, max_gap in bad:
+        assert lib.lidar_track_stream_f64(p, p, p, frames, c, carry, d, g, max_gap, p, p, p, p, p, p, None) == -1, (
+            frames, c, carry, d, g, max_gap)
+        assert lib.lidar_last_error().startswith(b"lidar_track_stream_f64: ")
+    bad = [(-1, cap, 0, 0, 1.0, 4, 4), (65536, cap, 0, 0, 1.0, 4, 4), (T, 0, 0, 0, 1.0, 4, 4),
+           (65535, 1 << 16, 0, 0, 1.0, 4, 4), (T, cap, -1, 0, 1.0, 4, 4), (T, cap, T + 1, 0, 1.0, 4, 4),
+           (T, cap, 0, 2, 1.0, 4, 4), (T, cap, 0, -1, 1.0, 4, 4), (T, cap, 0, 1, 0.0, 4, 4),
+           (T, cap, 0, 1, float("nan"), 4, 4), (T, cap, 0, 1, 1.0, 0, 4), (T, cap, 0, 1, 1.0, 4, 0),
+           (T, cap, 0, 1, 1.0, 1 << 16, 1 << 15)]
+    for frames, c, first, acc, g, nx, ny in bad:
+        assert lib.lidar_flow_cells_acc_f64(p, p, p, p, p, frames, c, first, acc, 0.0, 0.0, g, nx, ny, p, p, None) == -1, (
+            frames, c, first, acc, g, nx, ny)
+        assert lib.lidar_last_error().startswith(b"lidar_flow_cells_acc_f64: ")
+    assert lib.lidar_flow_cells_acc_f64(p, p, p, p, p, T, cap, 0, 1, 0.0, float("inf"), 1.0, 4, 4, p, p, None) == -1
+    # nothing to do, whatever the handle: no frames; only carried frames
+    assert lib.lidar_track_stream_f64(p, p, p, 0, cap, 0, dt, gate, 3, p, p, p, p, p, p, None) == 0
+    assert lib.lidar_track_stream_f64(p, p, p, 2, cap, 2, dt, gate, 1, p, p, p, p, p, p, None) == 0
+    assert lib.lidar_flow_cells_acc_f64(p, p, p, p, p, 0, cap, 0, 1, 0.0, 0.0, 1.0, 4, 4, p, p, None) == 0
+
+
+def test_python_validation_without_a_gpu():
+    from lidar_ai_recommendation_software_amd import people_tracking as pt
+    from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel
+    for bad in (-1, 8, 1.5):
+        with pytest.raises(ValueError, match="max_gap"):
+            pt.PeopleTracker(0.1, 0.3, max_gap=bad)
+        with pytest.raises(ValueError, match="max_gap"):
+            CrowdFlowModel().analyze_sequence([np.zeros((2, 2))], dt=0.1, x_range=(0.0, 1.0), y_range=(0.0, 1.0),
+                                              max_gap=bad)
+    for bad in (0.0, float("nan")):
+        with pytest.raises(ValueError, match="dt"):
+            pt.PeopleTracker(bad, 0.3)
+        with pytest.raises(ValueError, match="gate"):
+            pt.PeopleTracker(0.1, bad)
+    with pytest.raises(ValueError, match="x_range and y_range"):
+        pt.PeopleTracker(0.1, 0.3, x_range=(0.0, 1.0))
+    t = pt.PeopleTracker(0.1, 0.3, max_gap=2)
+    assert t.frames == 0 and t.max_gap == 2 and t.count is None and t.vsum is None
+    with pytest.raises(ValueError, match="contiguous CUDA"):
+        t.push(np.zeros((1, 4, 2)), np.zeros(1, dtype=np.int64))
+    with pytest.raises(ValueError, match="x_range"):
+        CrowdFlowModel().analyze_stream(t)
