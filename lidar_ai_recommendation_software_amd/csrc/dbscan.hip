@@ -138,62 +138,30 @@ __global__ void dbscan_cells_kernel(DbscanWs w, FrameMap fm)
     }
 }
 
-// --- exclusive scan of u32 over count = P[idx] (+extra) entries; out[count] = total
-constexpr int kScanPer = 4 * kT;
+// --- exclusive scan of u32 over count = P[idx] (+extra) entries; out[count] = total (tier_r.hpp's
+// scan_block_sum and scan_block, one frame per blockIdx.y)
 __global__ __launch_bounds__(kT) void scan_partial_kernel(DbscanWs w, const uint32_t *src, int idx, int64_t extra,
                                                           FrameMap fm)
 {
-    const uint32_t *in = fm.ws(src);
+    __shared__ uint32_t ws[kW];
     w = w.frame(fm);
-    const int64_t n = (int64_t)w.P[idx] + extra;
-    const int64_t b0 = (int64_t)blockIdx.x * kScanPer;
-    uint32_t v = 0;
-    for (int u = 0; u < 4; ++u) {
-        const int64_t i = b0 + threadIdx.x * 4 + u;
-        v += i < n ? in[i] : 0;
-    }
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __shared__ uint32_t ws[kW];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kW; ++w) t += ws[w];
-        w.partial[blockIdx.x] = t;
-    }
-}
-// one workgroup's kScanPer entries from b0 on (4 per thread): out[i] = base + the sum of in[b0 .. i) for
-// i < nout, entries from nin on counting 0.  in == out is fine: a thread reads its four before it writes them.
-__device__ __forceinline__ void scan_block(const uint32_t *in, int64_t nin, uint32_t *out, int64_t nout, int64_t b0,
-                                           uint32_t base)
-{
-    __shared__ uint32_t ws[kW];
-    uint32_t v[4], s = 0;
-    for (int u = 0; u < 4; ++u) {
-        const int64_t i = b0 + threadIdx.x * 4 + u;
-        v[u] = i < nin ? in[i] : 0;
-        s += v[u];
-    }
-    uint32_t e = base + block_excl_scan_u32(s, ws);
-    for (int u = 0; u < 4; ++u) {
-        const int64_t i = b0 + threadIdx.x * 4 + u;
-        if (i < nout) out[i] = e;
-        e += v[u];
-    }
+    scan_block_sum(fm.ws(src), (int64_t)w.P[idx] + extra, (int64_t)blockIdx.x * kScanPer, ws, &w.partial[blockIdx.x]);
 }
 __global__ __launch_bounds__(kT) void scan_top_kernel(DbscanWs w, int64_t nblk, FrameMap fm)
 {
+    __shared__ uint32_t ws[kW];
     uint32_t *partial = w.frame(fm).partial;
-    scan_block(partial, nblk, partial, nblk, 0, 0u);  // nblk <= kScanPer
+    scan_block(partial, nblk, partial, nblk, 0, 0u, ws);  // nblk <= kScanPer
 }
 __global__ __launch_bounds__(kT) void scan_final_kernel(DbscanWs w, const uint32_t *src, uint32_t *dst, int idx,
                                                         int64_t extra, FrameMap fm)
 {
+    __shared__ uint32_t ws[kW];
     w = w.frame(fm);
     const int64_t n = (int64_t)w.P[idx] + extra;
     const int64_t b0 = (int64_t)blockIdx.x * kScanPer;
     if (b0 > n) return;
-    scan_block(fm.ws(src), n, fm.ws(dst), n + 1, b0, w.partial[blockIdx.x]);  // out[n] = total
+    scan_block(fm.ws(src), n, fm.ws(dst), n + 1, b0, w.partial[blockIdx.x], ws);  // out[n] = total
 }
 
 __global__ void dbscan_scatter_kernel(DbscanWs w, FrameMap fm)

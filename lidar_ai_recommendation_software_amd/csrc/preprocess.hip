@@ -130,14 +130,7 @@ __device__ void block_seq_chain(const double *x, int64_t n, SeqStage &st, Step s
 // (tests/test_gpu_tier_r.py: the reference's goldens, byte-equal).
 constexpr int kChainMinRun = 16, kChainSeqRun = 32, kChainRowsPerLane = 4;
 
-// wave-uniform fp64 helpers (scalar registers: the chain's control flow stays scalar)
-__device__ __forceinline__ double readlane_d(double v, int l)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
+// wave-uniform fp64 helpers (scalar registers: the chain's control flow stays scalar); readlane_d: tier_r.hpp
 __device__ __forceinline__ double uniform_d(double v)
 {
     const uint64_t u = (uint64_t)__double_as_longlong(v);

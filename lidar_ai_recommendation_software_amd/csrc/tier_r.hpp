@@ -1,6 +1,7 @@
 // tier_r.hpp — what two of preprocess.hip, dbscan.hip and density_grid.hip share: sizes, the scalars slots,
 // the frame map, fp64 rounding wrappers, workgroup min / max / scan, the DBSCAN parameter block and workspace,
-// the venue grid's binning (density_grid.hip, track.hip),
+// the venue grid's binning (density_grid.hip, track.hip), the u32 scan's device code (dbscan.hip, track.hip),
+// readlane_d (preprocess.hip, track.hip),
 // and the host entry points of dbscan.hip and density_grid.hip for preprocess.hip and class_people.hip.  Kernels stay local to their translation unit.
 #pragma once
 #include <algorithm>
@@ -130,6 +131,56 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t *wt
     uint32_t base = 0;
     for (int w = w0; w < wave; ++w) base += wtot[w];
     return base + incl - v;
+}
+
+// ---- the device code of the three-launch exclusive u32 scan (per-workgroup sums, a scan of the sums, the
+// final pass); dbscan.hip and track.hip wrap it in __global__ kernels over their own arguments.
+constexpr int kScanPer = 4 * kT;  // entries per workgroup, 4 per thread
+// *total = the sum of the kScanPer entries of `in` from b0 on, entries from n on counting 0.  ws: kW words of LDS.
+__device__ __forceinline__ void scan_block_sum(const uint32_t *in, int64_t n, int64_t b0, uint32_t *ws, uint32_t *total)
+{
+    uint32_t v = 0;
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = b0 + threadIdx.x * 4 + u;
+        v += i < n ? in[i] : 0;
+    }
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kW; ++w) t += ws[w];
+        *total = t;
+    }
+}
+// kScanPer entries from b0 on: out[i] = base + the sum of in[b0 .. i) for i < nout, entries from nin on
+// counting 0; returns base + the sum of the thread's own and all earlier entries.  in == out is fine: a thread
+// reads its four before it writes them.  ws: kW words of LDS, free again after the caller's next barrier.
+__device__ __forceinline__ uint32_t scan_block(const uint32_t *in, int64_t nin, uint32_t *out, int64_t nout,
+                                               int64_t b0, uint32_t base, uint32_t *ws)
+{
+    uint32_t v[4], s = 0;
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = b0 + threadIdx.x * 4 + u;
+        v[u] = i < nin ? in[i] : 0;
+        s += v[u];
+    }
+    uint32_t e = base + block_excl_scan_u32(s, ws);
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = b0 + threadIdx.x * 4 + u;
+        if (i < nout) out[i] = e;
+        e += v[u];
+    }
+    return e;
+}
+
+// lane l's value of v in every lane (l wave-uniform: the result lives in scalar registers)
+__device__ __forceinline__ double readlane_d(double v, int l)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
 // ------------------------------------------------------------------ DBSCAN parameter block

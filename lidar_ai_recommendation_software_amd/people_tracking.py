@@ -18,18 +18,32 @@ from . import _native as nat
 from .global_density import venue_grid
 
 
+def _check_tensor(what, name, t, dev=None, dtype=None, shape=None):
+    """t is a contiguous CUDA tensor; with dev, on that device (people's); with dtype and shape, of those."""
+    on = dev is not None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or (on and t.device != dev):
+        raise ValueError(f"{what}: {name} must be a contiguous CUDA tensor" + (" on people's device" if on else ""))
+    if dtype is not None and (t.dtype != dtype or tuple(t.shape) != shape):
+        raise ValueError(f"{what}: {name} must be {shape} {dtype}, got {t.dtype} {tuple(t.shape)}")
+
+
 def _check_people(what, people, k):
-    for t in (people, k):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{what}: liblidar_amd operators take contiguous CUDA tensors")
+    _check_tensor(what, "people", people)
     if people.dtype != torch.float64 or people.dim() != 3 or people.shape[2] != 2 or people.shape[1] < 1:
         raise ValueError(f"{what}: people must be (T, cap, 2) float64 with cap >= 1")
     T = people.shape[0]
-    if k.dtype != torch.int64 or tuple(k.shape) != (T,):
-        raise ValueError(f"{what}: k must be ({T},) int64, got {k.dtype} {tuple(k.shape)}")
-    if k.device != people.device:
-        raise ValueError(f"{what}: people and k must be on the same device")
+    _check_tensor(what, "k", k, people.device, torch.int64, (T,))
     return T, people.shape[1]
+
+
+def _flow_cells_acc(people, k, prev, velocity, first, accumulate, grid, grid_size, count, vsum, slot):
+    """lidar_flow_cells_acc_f64 over checked tensors: the frames >= first into count / vsum, which it overwrites
+    (accumulate = 0) or continues (1); first = 1, accumulate = 0 is lidar_flow_cells_f64."""
+    x0, y0, nx, ny = grid
+    T, cap = people.shape[:2]
+    nat.call("lidar_flow_cells_acc_f64", nat.handle(people.device.index, slot), nat.ptr(people), nat.ptr(k),
+             nat.ptr(prev), nat.ptr(velocity), T, cap, first, accumulate, x0, y0, grid_size, nx, ny, nat.ptr(count),
+             nat.ptr(vsum), nat.stream_ptr())
 
 
 def _positive(what, name, v):
@@ -62,28 +76,20 @@ def track_people(people, k, dt, gate, slot=0):
 
 def flow_cells(people, k, prev, velocity, x_range, y_range, grid_size=1.0, slot=0):
     """The matched detections of track_people on the venue grid -> (count (nx, ny) int32, vsum (nx, ny, 2)
-    float64, (x0, y0, nx, ny)), device tensors, nothing synchronised (lidar_flow_cells_f64).  A matched
+    float64, (x0, y0, nx, ny)), device tensors, nothing synchronised (lidar_flow_cells_f64's computation).  A matched
     detection is binned by its own position with VenueGrid's binning; vsum adds the velocities of a cell's
     detections sequentially in (t, j) order, so it is the same bits on every run."""
     T, cap = _check_people("flow_cells", people, k)
-    for t in (prev, velocity):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.device != people.device:
-            raise ValueError("flow_cells: prev and velocity must be contiguous CUDA tensors on people's device")
-    if prev.dtype != torch.int32 or tuple(prev.shape) != (T, cap):
-        raise ValueError(f"flow_cells: prev must be ({T}, {cap}) int32, got {prev.dtype} {tuple(prev.shape)}")
-    if velocity.dtype != torch.float64 or tuple(velocity.shape) != (T, cap, 2):
-        raise ValueError(f"flow_cells: velocity must be ({T}, {cap}, 2) float64, got {velocity.dtype} "
-                         f"{tuple(velocity.shape)}")
+    _check_tensor("flow_cells", "prev", prev, people.device, torch.int32, (T, cap))
+    _check_tensor("flow_cells", "velocity", velocity, people.device, torch.float64, (T, cap, 2))
     g = _positive("flow_cells", "grid_size", grid_size)
-    x0, y0, nx, ny = venue_grid(x_range, y_range, g)
-    dev = people.device
+    grid = venue_grid(x_range, y_range, g)  # (x0, y0, nx, ny)
     with nat.grid_alloc():
-        count = torch.zeros((nx, ny), dtype=torch.int32, device=dev)  # T == 0: no detection
-        vsum = torch.zeros((nx, ny, 2), dtype=torch.float64, device=dev)
-    if T:
-        nat.call("lidar_flow_cells_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
-                 nat.ptr(velocity), T, cap, x0, y0, g, nx, ny, nat.ptr(count), nat.ptr(vsum), nat.stream_ptr())
-    return count, vsum, (x0, y0, nx, ny)
+        count = torch.zeros(grid[2:], dtype=torch.int32, device=people.device)  # T == 0: no detection
+        vsum = torch.zeros(grid[2:] + (2,), dtype=torch.float64, device=people.device)
+    if T:  # a frame-0 row has no predecessor in this call: first = 1
+        _flow_cells_acc(people, k, prev, velocity, 1, 0, grid, g, count, vsum, slot)
+    return count, vsum, grid
 
 
 # ------------------------------------------------------------------ continuous tracking (DESIGN.md §4.10)
@@ -121,15 +127,10 @@ def track_stream(people, k, dt, gate, max_gap=0, carry=0, state=None, ntracks=No
     if len(state) != len(STATE):
         raise ValueError("track_stream: state is (prev, gap, succ, velocity, track_id)")
     for t, (name, dtype, tail) in zip(state, STATE):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"track_stream: {name} must be a contiguous CUDA tensor on people's device")
-        if t.dtype != dtype or tuple(t.shape) != (T, cap) + tail:
-            raise ValueError(f"track_stream: {name} must be {(T, cap) + tail} {dtype}, got {t.dtype} {tuple(t.shape)}")
+        _check_tensor("track_stream", name, t, dev, dtype, (T, cap) + tail)
     if ntracks is None:
         ntracks = torch.zeros((), dtype=torch.int64, device=dev)
-    if (not isinstance(ntracks, torch.Tensor) or ntracks.dtype != torch.int64 or ntracks.dim() != 0
-            or ntracks.device != dev):
-        raise ValueError("track_stream: ntracks must be a () int64 tensor on people's device")
+    _check_tensor("track_stream", "ntracks", ntracks, dev, torch.int64, ())
     if T:
         prev, gap, succ, velocity, track_id = state
         nat.call("lidar_track_stream_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), T, cap, int(carry),
@@ -196,10 +197,8 @@ class PeopleTracker:
                                                               self.ntracks, self.slot)
         self.matched += (prev[C:] >= 0).sum()
         if self.grid is not None:
-            x0, y0, nx, ny = self.grid
-            nat.call("lidar_flow_cells_acc_f64", nat.handle(dev.index, self.slot), nat.ptr(people), nat.ptr(k),
-                     nat.ptr(prev), nat.ptr(velocity), C + T, cap, C, 1, x0, y0, self.grid_size, nx, ny,
-                     nat.ptr(self.count), nat.ptr(self.vsum), nat.stream_ptr())
+            _flow_cells_acc(people, k, prev, velocity, C, 1, self.grid, self.grid_size, self.count, self.vsum,
+                            self.slot)
         self.frames += T
         keep = min(self.max_gap + 1, self.frames)
         self._carry = tuple(t[C + T - keep:] for t in (people, k, prev, gap, succ, velocity, track_id))

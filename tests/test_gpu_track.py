@@ -76,6 +76,19 @@ def test_block_and_tile_edges(cuda):
     check(run(cuda, people, k, ref.DT, 0.25), want)
 
 
+def test_one_frame_and_cap_1(cuda):
+    """The smallest fwd / bwd, which take frames * cap entries indexed by a pair's start frame: one frame (no pair
+    at all) and two frames of cap 1 (one entry per frame), matched, out of the gate, and with an empty side."""
+    people, k = ref.planted_sequence(*ref.PLANTED[0])
+    check(run(cuda, people[:1], k[:1], ref.DT, 0.25), ref.track_spec(people[:1], k[:1], ref.DT, 0.25), "one frame")
+    two = np.array([[[1.0, 2.0]], [[1.0 + ref.STEP, 2.0 - ref.STEP]]])
+    for k2, gate in (((1, 1), 0.25), ((1, 1), ref.STEP), ((0, 1), 0.25), ((1, 0), 0.25)):
+        k2 = np.array(k2, dtype=np.int64)
+        want = ref.track_spec(two, k2, ref.DT, gate)
+        assert int(np.sum(want["prev"] >= 0)) == (1 if gate == 0.25 and k2.all() else 0)
+        check(run(cuda, two, k2, ref.DT, gate), want, f"cap 1, k {k2.tolist()}, gate {gate}")
+
+
 def test_k_above_cap_and_junk_rows(cuda):
     case = ref.PLANTED[1]
     people, k = ref.planted_sequence(*case)
