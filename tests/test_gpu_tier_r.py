@@ -156,7 +156,8 @@ class DiagVoxel:
     """The diagnostic build (liblidar_amd_diag.so, `make diag`): the product library plus its testing aids
     (lidar_debug_fill_workspace / _set_epoch / _voxel_inject), which the product ABI does not export.  It is
     loaded beside the product library and keeps handles of its own, so the voxel calls below run the diag
-    build's copy of csrc/voxel_batch.hip (the same source)."""
+    build's copy of the batched voxel path (csrc/voxel_batch.hip, voxel_keys.hip, voxel_bucket.hip: the
+    same sources)."""
 
     _lib = None
 
@@ -349,6 +350,30 @@ def test_voxel_bucket_sort_paths(cuda, case):
         assert np.array_equal(c[f, :nv[f]].view(np.uint32), wc.view(np.uint32)), (case, f)
     c1, vid1, cnt1 = dp.voxel_downsample(x, v)
     assert np.array_equal(vid1, vid[0]) and np.array_equal(c1.view(np.uint32), c[0, :nv[0]].view(np.uint32))
+
+
+@pytest.mark.parametrize("n", [128, 129, 2048, 2049, 2560, 2561])
+def test_voxel_bucket_path_seams(cuda, n):
+    """The seams of the bucket launch's path choice, with every point of the frame in one voxel (one run of
+    n equal keys, all in bucket 0): 128 / 129 straddle SEGMAX (counting sort / bitonic), 2 048 / 2 049
+    BITONIC_P (bitonic / radix in a bucket within CAP), 2 560 / 2 561 CAP (the pairs loaded and the counting
+    sort tried and left / the bucket straight to the radix sort).  From 2 049 points on the frame has a
+    second bucket (ceil(n / 2 048)), empty, whose count of 0 still goes out for the look-back.  Bit-exact
+    against the oracle through the batched path (two frames) and the drop-in."""
+    import torch
+    from lidar_ai_recommendation_software_amd import pointnet2 as pn
+    x, v = np.random.default_rng(77).uniform(-1, 1, (n, 3)).astype(np.float32), 100.0
+    xb = np.stack([x, x[::-1].copy()])
+    c, vid, cnt, nv = (t.cpu().numpy() for t in pn.voxel_downsample_batch(torch.from_numpy(xb).to(cuda), v))
+    for f in range(2):
+        wc, wvid, wcnt = tier_n.voxel_downsample(xb[f], v)
+        assert len(wcnt) == 1 and wcnt[0] == n
+        assert nv[f] == 1, (n, f)
+        assert np.array_equal(vid[f], wvid) and np.array_equal(cnt[f, :1], wcnt), (n, f)
+        assert np.array_equal(c[f, :1].view(np.uint32), wc.view(np.uint32)), (n, f)
+    c1, vid1, cnt1 = dp.voxel_downsample(x, v)  # (frame 0 above: equal to the oracle)
+    assert np.array_equal(vid1, vid[0]) and np.array_equal(cnt1, cnt[0, :1]), n
+    assert np.array_equal(c1.view(np.uint32), c[0, :1].view(np.uint32)), n
 
 
 @pytest.mark.parametrize("seed", range(12))

@@ -1,6 +1,12 @@
 """Phase cycles of the fused voxel keys launch (diagnostic build -DVX_DIAG_KEYS: s_memtime stamps of
-workgroup thread 0, written into the tail rows of each frame's centroids).  usage:
-LIDAR_AMD_LIB=tools/ablib/liblidar_vx_KEYS.so python tools/micro/voxel_keys_phases.py [B] [voxel]"""
+workgroup thread 0, 12 words per tile written into the tail rows of each frame's centroids).  Every
+stamp also takes the 100 MHz clock (before the split into voxel_keys.hip: the first and last only),
+about as much again per stamp, so its cycles do not compare with older records.  Build the library
+(into a build_* directory, which git ignores and `make clean` removes), then run with it:
+  HIPCC_COMPILE_FLAGS_APPEND=-DVX_DIAG_KEYS make -C lidar_ai_recommendation_software_amd/csrc \
+      BUILD=build_vxkeys OUT=build_vxkeys/liblidar_amd.so
+  LIDAR_AMD_LIB=lidar_ai_recommendation_software_amd/csrc/build_vxkeys/liblidar_amd.so \
+      python tools/micro/voxel_keys_phases.py [B] [voxel]"""
 import os
 import sys
 

@@ -1,7 +1,12 @@
 """Phase cycles of the voxel bucket kernel (diagnostic build -DVX_DIAG_PHASES: s_memtime and
 s_memrealtime stamps of workgroup thread 0, written into the scratch tail of the counts output,
-16 words per bucket).  usage:
-LIDAR_AMD_LIB=tools/ablib/liblidar_vx_PHASES.so python tools/micro/voxel_phases.py [B] [voxel]"""
+16 words per bucket; word 7, the look-back's polls, is now filled on the bitonic / radix paths too,
+where it was 0).  Build the library (into a build_* directory, which git ignores and `make clean`
+removes), then run with it:
+  HIPCC_COMPILE_FLAGS_APPEND=-DVX_DIAG_PHASES make -C lidar_ai_recommendation_software_amd/csrc \
+      BUILD=build_vxphases OUT=build_vxphases/liblidar_amd.so
+  LIDAR_AMD_LIB=lidar_ai_recommendation_software_amd/csrc/build_vxphases/liblidar_amd.so \
+      python tools/micro/voxel_phases.py [B] [voxel]"""
 import os
 import sys
 
