@@ -546,6 +546,44 @@ int lidar_flow_cells_acc_f64(lidar_handle *h, const double *people, const int64_
                              int32_t accumulate, double x0, double y0, double grid, int64_t nx, int64_t ny,
                              int32_t *count, double *vsum, void *stream);
 
+/* Gate counts and zone occupancy from tracked people (csrc/track_events.hip; DESIGN.md §3 "Gate and zone
+ * events", §4.12): what the links of lidar_track_people_f64 / lidar_track_stream_f64 say about lines and
+ * areas of the venue.  Asynchronous like its siblings: every pointer a device pointer, no host
+ * synchronisation, nothing read back, no scratch.  All arithmetic fp64, one rounding per operation.
+ *
+ * lidar_track_events_f64: people, k, frames, cap and K_t as lidar_track_people_f64; prev (frames, cap) int32;
+ * gap (frames, cap) int32 or null (null: every link spans one frame, lidar_track_people_f64's prev).  Only
+ * the frames t >= first are evaluated (with a carry in front: first = carry, as lidar_flow_cells_acc_f64).
+ * A row (t, j), j < K_t, is linked iff, with i = prev[t][j] and g = gap ? gap[t][j] : 1: i >= 0 and
+ * 1 <= g <= 8 and g <= t and i < K_(t-g); then P = people[t-g][i] and Q = people[t][j].  Every other row is
+ * unlinked: no content of prev / gap makes the call read outside people.
+ * gates (ngates, 4), rows (ax, ay, bx, by).  side(a, b, p) = ((b.x - a.x) * (p.y - a.y)) - ((b.y - a.y) *
+ * (p.x - a.x)); sP = side(A, B, P), sQ = side(A, B, Q), sA = side(P, Q, A), sB = side(P, Q, B).  The link
+ * crosses the gate iff all four are finite and (sP >= 0) != (sQ >= 0) and (sA >= 0) != (sB >= 0); the
+ * crossing is forward iff sQ >= 0 (from the right of A -> B to its left or onto it), backward otherwise.  A
+ * detection exactly on the line counts as left, so a track that steps onto the line and then on counts once;
+ * P == Q, A == B and a gate with a non-finite coordinate never cross: the tables need no validation here.
+ * zones (nzones, 4), rows (x0, x1, y0, y1).  inside(z, p) = x0 <= p.x && p.x < x1 && y0 <= p.y && p.y < y1
+ * (a NaN: false).
+ * Outputs, indexed by t - first, every element written.  gate_counts (frames - first, ngates, 2) int32: the
+ * forward and the backward crossings of the frame's linked rows (a crossing belongs to the frame of Q).
+ * zone_counts (frames - first, nzones, 3) int32: [0] occupancy, the rows j < K_t with inside(Q), linked or
+ * not; [1] entries, the linked rows with inside(Q) && !inside(P); [2] exits, the linked rows with inside(P)
+ * && !inside(Q) (a new detection inside a zone is occupancy, not an entry).  gate_fwd, gate_bwd, zone_in
+ * (frames - first, cap) int64: bit g / z set for the gates the row crossed forward / backward and the zones
+ * that hold it (with track_id: the unique tracks per gate); rows at or past K_t get 0.  All results are
+ * integers, the same under every schedule.
+ *
+ * LIDAR_EINVAL: a null handle, people, k or prev; frames < 0 or > 65535, cap < 1, frames * cap >= 2^31;
+ * first outside 0 .. frames; ngates or nzones outside 0 .. 64, or both 0; with ngates > 0 a null gates,
+ * gate_counts, gate_fwd or gate_bwd, with nzones > 0 a null zones, zone_counts or zone_in (the pointers of a
+ * kind whose count is 0 are not used).  frames == first returns LIDAR_OK and writes nothing. */
+int lidar_track_events_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                           const int32_t *gap, int64_t frames, int64_t cap, int64_t first, const double *gates,
+                           int32_t ngates, const double *zones, int32_t nzones, int32_t *gate_counts,
+                           int32_t *zone_counts, int64_t *gate_fwd, int64_t *gate_bwd, int64_t *zone_in,
+                           void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

@@ -50,8 +50,24 @@ class CrowdFlowModel:
         return {"flow_vectors": flow_vectors, "avg_speed": avg_speed,
                 "dominant_direction": dominant_direction, "bottlenecks": bottlenecks}
 
+    @staticmethod
+    def _event_keys(K, gate_total, zone_total, events):
+        """The gate and zone keys of analyze_sequence / analyze_stream from the host copies of the totals
+        (G, 2) and (Z, 2) and of track_events' five arrays over the frames K (a mask None: that kind is absent)."""
+        gate_counts, zone_counts, gate_fwd, gate_bwd, zone_in = events
+        rows = range(len(K))
+
+        def sliced(mask):
+            return [np.zeros(K[t], dtype=np.int64) if mask is None else mask[t, :K[t]] for t in rows]
+
+        return {"gate_counts": gate_total.astype(np.int64), "gate_series": gate_counts,
+                "zone_occupancy": zone_counts[:, :, 0], "zone_entries": zone_total[:, 0].astype(np.int64),
+                "zone_exits": zone_total[:, 1].astype(np.int64),
+                "gate_events": {"forward": sliced(gate_fwd), "backward": sliced(gate_bwd)},
+                "zone_membership": sliced(zone_in)}
+
     def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
-                         min_observations=1, max_gap=0):
+                         min_observations=1, max_gap=0, gates=None, zones=None):
         """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
 
         people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
@@ -71,7 +87,16 @@ class CrowdFlowModel:
         (``people_tracking.track_stream``, DESIGN.md §3 "Continuous people tracking"): a detection is also
         associated with the open detections up to max_gap + 1 frames back, and its velocity is the displacement
         over that many dt.  The result then also holds gaps: per frame (K_t,) int32, the frame distance to each
-        row's predecessor (0: none)."""
+        row's predecessor (0: none).
+
+        gates (G, 4) rows (ax, ay, bx, by) and / or zones (Z, 4) rows (x0, x1, y0, y1), array-likes as
+        ``people_tracking.check_gates`` / ``check_zones`` take them (at most 64 each): the tracks' crossings of
+        the gate lines and their presence in the zones (``people_tracking.track_events``, DESIGN.md §3 "Gate and
+        zone events"), in the same read-back.  The result then also holds gate_counts (G, 2) int64, the forward
+        and backward crossings (forward: from the right of A -> B to its left); gate_series (T, G, 2) int32 per
+        frame; zone_occupancy (T, Z) int32; zone_entries / zone_exits (Z,) int64; gate_events {"forward",
+        "backward"} and zone_membership: per frame (K_t,) int64, bit g / z set for the gates the row crossed
+        and the zones that hold it.  An absent kind has G or Z = 0 and zero masks."""
         import torch
         from . import people_tracking as pt
 
@@ -95,6 +120,8 @@ class CrowdFlowModel:
             raise ValueError(f"analyze_sequence: min_observations must be an integer >= 1, got {min_observations}")
         if int(max_gap) != max_gap or not 0 <= max_gap <= pt.MAX_GAP:
             raise ValueError(f"analyze_sequence: max_gap must be an integer in 0 .. {pt.MAX_GAP}, got {max_gap}")
+        gates = None if gates is None else pt.check_gates(gates)
+        zones = None if zones is None else pt.check_zones(zones)
         if isinstance(people, torch.Tensor):
             if k is None:
                 raise ValueError("analyze_sequence: a people tensor needs k")
@@ -118,7 +145,11 @@ class CrowdFlowModel:
             prev, gap, _, velocity, track_id, ntracks = pt.track_stream(people, k, dt, gate, max_gap)
         count, vsum, _ = pt.flow_cells(people, k, prev, velocity, x_range, y_range, grid_size)
         dev = [k, prev, track_id, velocity, ntracks, count, vsum] + ([] if gap is None else [gap])
-        host = [t.to("cpu", non_blocking=True) for t in dev]
+        events = ()
+        if gates is not None or zones is not None:
+            tables = [None if t is None else torch.from_numpy(t).to(people.device) for t in (gates, zones)]
+            events = pt.track_events(people, k, prev, gap, *tables)
+        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + list(events)]
         torch.cuda.current_stream(people.device).synchronize()  # the one read-back
         kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host[:7])
         K = np.minimum(np.maximum(kh, 0), people.shape[1])
@@ -128,6 +159,9 @@ class CrowdFlowModel:
         if gap is not None:
             gap = host[7].numpy()
             extras["gaps"] = [gap[t, :K[t]] for t in range(len(K))]
+        if events:
+            ev = [None if t is None else t.numpy() for t in host[len(dev):]]
+            extras.update(self._event_keys(K, ev[0].sum(axis=0), ev[1][:, :, 1:].sum(axis=0), ev))
         return self._measured_flow(count, vsum, x_range, y_range, grid_size, min_observations, extras)
 
     def analyze_stream(self, tracker, min_observations=1):
@@ -135,7 +169,9 @@ class CrowdFlowModel:
         extent: ``analyze_sequence``'s keys (``gaps`` included) from the tracker's accumulated cells, with one
         read-back.  tracks / matched count the whole stream; track_ids / velocities / gaps are per frame for
         the frames the tracker still holds, its last min(max_gap + 1, frames) ones (the rows of earlier frames
-        were returned by ``push``)."""
+        were returned by ``push``).  A tracker built with gates / zones adds ``analyze_sequence``'s gate and zone
+        keys, in the same read-back: gate_counts, zone_entries and zone_exits total the whole stream;
+        gate_series, zone_occupancy, gate_events and zone_membership cover the held frames."""
         import torch
 
         if int(min_observations) != min_observations or min_observations < 1:
@@ -144,17 +180,26 @@ class CrowdFlowModel:
             raise ValueError("analyze_stream: the tracker was built without x_range / y_range: it holds no flow cells")
         if tracker.frames == 0:
             extras = {"tracks": 0, "matched": 0, "track_ids": [], "velocities": [], "gaps": []}
+            if tracker.events:
+                G, Z = (0 if t is None else t.shape[0] for t in tracker._tables)
+                none = (np.zeros((0, G, 2), dtype=np.int32), np.zeros((0, Z, 3), dtype=np.int32), None, None, None)
+                extras.update(self._event_keys([], np.zeros((G, 2), dtype=np.int64), np.zeros((Z, 2), dtype=np.int64),
+                                               none))
             return self._measured_flow(None, None, None, None, None, min_observations, extras)
         _, k, _, gap, _, velocity, track_id = tracker._carry
-        dev = (k, gap, velocity, track_id, tracker.ntracks, tracker.matched, tracker.count, tracker.vsum)
-        host = [t.to("cpu", non_blocking=True) for t in dev]
+        dev = [k, gap, velocity, track_id, tracker.ntracks, tracker.matched, tracker.count, tracker.vsum]
+        events = [tracker.gate_total, tracker.zone_total, *tracker._held_events] if tracker.events else []
+        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + events]
         torch.cuda.current_stream(k.device).synchronize()  # the one read-back
-        kh, gap, velocity, track_id, ntracks, matched, count, vsum = (t.numpy() for t in host)
+        kh, gap, velocity, track_id, ntracks, matched, count, vsum = (t.numpy() for t in host[:8])
         K = np.minimum(np.maximum(kh, 0), tracker.cap)
         extras = {"tracks": int(ntracks), "matched": int(matched),
                   "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
                   "velocities": [velocity[t, :K[t]] for t in range(len(K))],
                   "gaps": [gap[t, :K[t]] for t in range(len(K))]}
+        if events:
+            ev = [None if t is None else t.numpy() for t in host[8:]]
+            extras.update(self._event_keys(K, ev[0], ev[1], ev[2:]))
         return self._measured_flow(count, vsum, tracker.x_range, tracker.y_range, tracker.grid_size, min_observations,
                                    extras)
 

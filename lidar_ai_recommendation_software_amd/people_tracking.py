@@ -9,9 +9,15 @@ cell in a fixed order.  Both are asynchronous: device tensors in, device tensors
 On a live feed (DESIGN.md §3 "Continuous people tracking", §4.10) ``PeopleTracker`` takes batch after batch:
 its ids last across ``push`` calls and a track survives up to ``max_gap`` frames without a detection;
 ``track_stream`` is the call underneath (lidar_track_stream_f64), with the carried frames' state explicit.
+
+``track_events`` (csrc/track_events.hip; DESIGN.md §3 "Gate and zone events", §4.12) turns the links into counts:
+crossings of gate lines, forward and backward, and occupancy, entries and exits of zones, per frame, with a bit
+mask per row; ``check_gates`` / ``check_zones`` validate a user's tables on the host, and
+``PeopleTracker(gates=, zones=)`` totals the counts across ``push`` calls.
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -139,6 +145,99 @@ def track_stream(people, k, dt, gate, max_gap=0, carry=0, state=None, ntracks=No
     return (*state, ntracks)
 
 
+# ------------------------------------------------------------------ gate and zone events
+MAX_TABLE = 64  # gates, and zones, per call: a bit of an int64 mask each
+
+
+def _check_table(what, name, rows):
+    a = np.ascontiguousarray(rows, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 4 or not 1 <= a.shape[0] <= MAX_TABLE:
+        raise ValueError(f"{what}: {name} must be (n, 4) with 1 <= n <= {MAX_TABLE}, got {a.shape}")
+    for r, row in enumerate(a):
+        if not np.all(np.isfinite(row)):
+            raise ValueError(f"{what}: row {r} is not finite: {row.tolist()}")
+    return a
+
+
+def check_gates(gates):
+    """Array-like (G, 4) rows (ax, ay, bx, by), 1 <= G <= 64, finite, A != B -> contiguous float64 ndarray;
+    ValueError names the offending row.  Host only: no GPU or library call."""
+    a = _check_table("check_gates", "gates", gates)
+    for r, (ax, ay, bx, by) in enumerate(a):
+        if ax == bx and ay == by:
+            raise ValueError(f"check_gates: row {r} is degenerate (A == B): {a[r].tolist()}")
+    return a
+
+
+def check_zones(zones):
+    """Array-like (Z, 4) rows (x0, x1, y0, y1), 1 <= Z <= 64, finite, x0 < x1 and y0 < y1 -> contiguous float64
+    ndarray; ValueError names the offending row.  Host only: no GPU or library call."""
+    a = _check_table("check_zones", "zones", zones)
+    for r, (x0, x1, y0, y1) in enumerate(a):
+        if not (x0 < x1 and y0 < y1):
+            raise ValueError(f"check_zones: row {r} needs x0 < x1 and y0 < y1: {a[r].tolist()}")
+    return a
+
+
+def _event_shapes(nf, cap, G, Z):
+    """(name, dtype, shape) of track_events' five outputs; a mask of an absent kind is None."""
+    return (("gate_counts", torch.int32, (nf, G, 2)), ("zone_counts", torch.int32, (nf, Z, 3)),
+            ("gate_fwd", torch.int64, (nf, cap) if G else None), ("gate_bwd", torch.int64, (nf, cap) if G else None),
+            ("zone_in", torch.int64, (nf, cap) if Z else None))
+
+
+def track_events(people, k, prev, gap=None, gates=None, zones=None, first=0, out=None, slot=0):
+    """Gate crossings and zone occupancy of the links (prev, gap) track_people / track_stream left on the device
+    (lidar_track_events_f64; DESIGN.md §3 "Gate and zone events").  people (T, cap, 2), k (T,), prev (T, cap)
+    int32; gap (T, cap) int32, or None for track_people's prev (every link spans one frame); gates (G, 4) and
+    zones (Z, 4): float64 device tensors, at least one of them, 1 .. 64 rows each (check_gates / check_zones
+    validate what a user passes; here only device, dtype and shape are checked); only the frames t >= first
+    are evaluated.  -> (gate_counts (T - first, G, 2) int32 forward / backward, zone_counts (T - first, Z, 3)
+    int32 occupancy / entries / exits, gate_fwd, gate_bwd, zone_in (T - first, cap) int64 bit masks per row),
+    device tensors, nothing synchronised; an absent kind has G or Z = 0 and None for its masks.  out: the five
+    preallocated (None where the result has None); every element is written, none when first == T."""
+    what = "track_events"
+    T, cap = _check_people(what, people, k)
+    dev = people.device
+    _check_tensor(what, "prev", prev, dev, torch.int32, (T, cap))
+    if gap is not None:
+        _check_tensor(what, "gap", gap, dev, torch.int32, (T, cap))
+    if gates is None and zones is None:
+        raise ValueError(f"{what}: needs gates or zones")
+    n = {}
+    for name, t in (("gates", gates), ("zones", zones)):
+        n[name] = 0
+        if t is not None:
+            _check_tensor(what, name, t, dev)
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or not 1 <= t.shape[0] <= MAX_TABLE:
+                raise ValueError(f"{what}: {name} must be (n, 4) float64 with 1 <= n <= {MAX_TABLE}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+            n[name] = t.shape[0]
+    if int(first) != first or not 0 <= first <= T:
+        raise ValueError(f"{what}: first must be an integer in 0 .. T = {T}, got {first}")
+    first = int(first)
+    shapes = _event_shapes(T - first, cap, n["gates"], n["zones"])
+    given = (None,) * len(shapes) if out is None else tuple(out)
+    if len(given) != len(shapes):
+        raise ValueError(f"{what}: out is (gate_counts, zone_counts, gate_fwd, gate_bwd, zone_in)")
+    out = []
+    for t, (name, dtype, shape) in zip(given, shapes):
+        if shape is None:
+            if t is not None:
+                raise ValueError(f"{what}: out's {name} must be None without its table")
+        elif t is None:  # a None among out is allocated like all of them without out
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        else:
+            _check_tensor(what, name, t, dev, dtype, shape)
+        out.append(t)
+    out = tuple(out)
+    if T > first:  # an empty tensor has no address to pass
+        nat.call("lidar_track_events_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
+                 nat.ptr(gap), T, cap, first, nat.ptr(gates), n["gates"], nat.ptr(zones), n["zones"],
+                 *(nat.ptr(t) if t is not None and t.numel() else None for t in out), nat.stream_ptr())
+    return out
+
+
 class PeopleTracker:
     """A sensor's people tracked batch after batch: ids that last across push() calls, tracks stitched over up
     to max_gap missed frames, and (with a venue extent) the flow cells of everything pushed so far.
@@ -150,9 +249,18 @@ class PeopleTracker:
     Whatever the batch sizes, the outputs are those of one call over the whole stream, bit for bit.  Nothing
     is synchronised.  ntracks () int64, matched () int64 (detections with a measured velocity), count (nx, ny)
     int32 and vsum (nx, ny, 2) float64 are device tensors (count / vsum None without an extent); frames is the
-    number of frames seen."""
+    number of frames seen.
 
-    def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0):
+    gates (G, 4) and / or zones (Z, 4), array-likes as check_gates / check_zones take them, are validated here
+    and uploaded once, at the first push; push then also calls lidar_track_events_f64(first = carry) and adds the
+    new frames' counts into gate_total (G, 2) int64 (forward, backward) and zone_total (Z, 2) int64 (entries,
+    exits), device tensors (G or Z = 0 for an absent kind; occupancy is per frame and not accumulated).
+    last_events: track_events' five arrays for the frames of the last push.  However the stream is cut into
+    pushes, the concatenated last_events and the totals are those of one call over the whole stream.  Without
+    gates and zones the three stay None and push makes no further call."""
+
+    def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0, gates=None,
+                 zones=None):
         self.dt, self.gate = _positive("PeopleTracker", "dt", dt), _positive("PeopleTracker", "gate", gate)
         self.max_gap = _max_gap("PeopleTracker", max_gap)
         if (x_range is None) != (y_range is None):
@@ -166,6 +274,10 @@ class PeopleTracker:
         self.cap = None
         self.ntracks = self.matched = self.count = self.vsum = None
         self._carry = None  # (people, k, prev, gap, succ, velocity, track_id) of the last frames
+        self._tables = (None if gates is None else check_gates(gates), None if zones is None else check_zones(zones))
+        self.events = any(t is not None for t in self._tables)
+        self.gate_total = self.zone_total = self.last_events = None
+        self._held_events = None  # track_events' arrays of the frames in _carry
 
     def push(self, people, k):
         """-> (prev, gap, track_id, velocity) of the T new frames, device tensors."""
@@ -181,6 +293,13 @@ class PeopleTracker:
                     self.vsum = torch.zeros(self.grid[2:] + (2,), dtype=torch.float64, device=dev)
             self._carry = (people[:0], k[:0]) + tuple(torch.empty((0, cap) + tail, dtype=dtype, device=dev)
                                                       for _, dtype, tail in STATE)
+            if self.events:
+                self._tables = tuple(None if t is None else torch.from_numpy(t).to(dev) for t in self._tables)
+                G, Z = (0 if t is None else t.shape[0] for t in self._tables)
+                self.gate_total = torch.zeros((G, 2), dtype=torch.int64, device=dev)
+                self.zone_total = torch.zeros((Z, 2), dtype=torch.int64, device=dev)
+                self._held_events = tuple(None if shape is None else torch.empty(shape, dtype=dtype, device=dev)
+                                          for _, dtype, shape in _event_shapes(0, cap, G, Z))
         if cap != self.cap or dev != self.ntracks.device:
             raise ValueError(f"PeopleTracker.push: cap and device are fixed by the first push ({self.cap}, "
                              f"{self.ntracks.device}), got {cap}, {dev}")
@@ -188,6 +307,8 @@ class PeopleTracker:
             raise ValueError(f"PeopleTracker.push: {self.frames + T} frames of {cap} rows could pass 2^31 track ids")
         C = self._carry[0].shape[0]
         if T == 0:
+            if self.events:
+                self.last_events = tuple(None if t is None else t[C:] for t in self._held_events)
             return tuple(self._carry[i][C:] for i in (2, 3, 6, 5))
         people = torch.cat([self._carry[0], people])
         k = torch.cat([self._carry[1], k])
@@ -201,5 +322,11 @@ class PeopleTracker:
                             self.slot)
         self.frames += T
         keep = min(self.max_gap + 1, self.frames)
+        if self.events:
+            self.last_events = track_events(people, k, prev, gap, *self._tables, first=C, slot=self.slot)
+            self.gate_total += self.last_events[0].sum(dim=0, dtype=torch.int64)
+            self.zone_total += self.last_events[1][:, :, 1:].sum(dim=0, dtype=torch.int64)
+            self._held_events = tuple(None if t is None else torch.cat([h, t])[C + T - keep:]
+                                      for h, t in zip(self._held_events, self.last_events))
         self._carry = tuple(t[C + T - keep:] for t in (people, k, prev, gap, succ, velocity, track_id))
         return prev[C:], gap[C:], track_id[C:], velocity[C:]
