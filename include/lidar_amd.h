@@ -584,6 +584,46 @@ int lidar_track_events_f64(lidar_handle *h, const double *people, const int64_t 
                            int32_t *zone_counts, int64_t *gate_fwd, int64_t *gate_bwd, int64_t *zone_in,
                            void *stream);
 
+/* Track history (csrc/track_history.hip; DESIGN.md §3 "Track history", §4.13): per detection, how long its
+ * track has lived, how often it was seen, how far it walked, where it started and how long it has been in
+ * each zone; per frame and zone, the stays that ended.  Asynchronous like its siblings: every pointer a device
+ * pointer, no host synchronisation, nothing read back; scratch (4 bytes per row) from the handle's workspace.
+ * All arithmetic fp64, one rounding per operation, the square root correctly rounded.
+ *
+ * lidar_track_history_f64: people, k, prev, gap (or null), frames, cap, K_t and the link guard exactly as
+ * lidar_track_events_f64: a row (t, j), j < K_t, is linked iff, with i = prev[t][j] and g = gap ? gap[t][j] : 1:
+ * i >= 0 and 1 <= g <= 8 and g <= t and i < K_(t-g); its source is the row (s, i), s = t - g, P = people[s][i],
+ * Q = people[t][j].  No content of prev / gap makes the call read or write outside the arrays.
+ * zones (nzones, 4) rows (x0, x1, y0, y1), 0 <= nzones <= 64, inside() as lidar_track_events_f64.
+ * carry = C, 0 <= C <= frames: the leading frames whose history state is given; they are never written.
+ * Heirs: among the rows of frames >= C that are linked to the same source, the lowest in (t, j) order is the
+ * source's heir and continues its history; every other row of a frame >= C, unlinked or a linked non-heir,
+ * starts a history.  (lidar_track_people_f64 and lidar_track_stream_f64 name a source at most once: on their
+ * links every linked row is an heir.)
+ * State, (frames, ...) arrays, every element of the frames >= C written:
+ *   age (frames, cap) int32, frames since the history's first detection: 0 for a start, age[s][i] + g for a
+ *     row that continues (s, i), -1 at or past K_t;
+ *   hits (frames, cap) int32, detections so far: 1, hits[s][i] + 1, 0;
+ *   path (frames, cap) fp64, metres walked: 0.0, path[s][i] + sqrt((dx*dx) + (dy*dy)) with dx = Q.x - P.x and
+ *     dy = Q.y - P.y, 0.0 (a NaN coordinate makes it NaN from there on; a NaN's payload and sign are free);
+ *   origin (frames, cap, 2) fp64, the first detection's position: Q, origin[s][i], (0, 0);
+ *   stay (frames, cap, nzones) int32 (nzones > 0), frames since the present unbroken presence in zone z
+ *     began: inside(z, Q) ? 0 : -1 for a start; inside(z, Q) ? (stay[s][i][z] >= 0 ? stay[s][i][z] + g : 0)
+ *     : -1 for a row that continues; -1 at or past K_t.
+ * dwell (frames - C, nzones, 3) int64 (nzones > 0), indexed by t - C, every element written: each continuing
+ * row of frame t with stay[s][i][z] >= 0 and !inside(z, Q) (the track has left zone z) adds 1 to [0] and
+ * stay[s][i][z] to [1] and raises [2] to stay[s][i][z].  A stay's length runs from its first to its last
+ * detection inside (one detection: 0); a history that ends inside a zone is not a completed stay.  Integers:
+ * the same under every schedule.  On the two tracking calls' links dwell[..][z][0] is zone_counts[..][z][2].
+ *
+ * LIDAR_EINVAL: a null handle, people, k, prev, age, hits, path or origin; frames < 0 or > 65535, cap < 1,
+ * frames * cap >= 2^31; carry outside 0 .. frames; nzones outside 0 .. 64; with nzones > 0 a null zones, stay
+ * or dwell (unused with nzones == 0).  frames == carry returns LIDAR_OK and writes nothing. */
+int lidar_track_history_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                            const int32_t *gap, int64_t frames, int64_t cap, int64_t carry, const double *zones,
+                            int32_t nzones, int32_t *age, int32_t *hits, double *path, double *origin,
+                            int32_t *stay, int64_t *dwell, void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

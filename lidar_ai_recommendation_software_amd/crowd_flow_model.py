@@ -66,8 +66,49 @@ class CrowdFlowModel:
                 "gate_events": {"forward": sliced(gate_fwd), "backward": sliced(gate_bwd)},
                 "zone_membership": sliced(zone_in)}
 
+    @staticmethod
+    def track_table(track_id, age, hits, path, origin, people, K, frames, dt):
+        """One entry per track present in the rows read back, from each track's last row in (t, j) order: host
+        arrays (n, cap[, 2]) over n frames with K live rows each, frames (n,) their frame numbers -> dict of equally
+        long arrays, ascending in track_id: track_id int32, first_frame = last_frame - age and last_frame int64,
+        hits int32, path_length, displacement (|last position - origin|) and mean_speed (path_length / (age * dt),
+        0.0 where age is 0) float64."""
+        K = np.asarray(K, dtype=np.int64)
+        live = np.arange(track_id.shape[1] if len(K) else 0)[None, :] < K[:, None]
+        r, j = np.nonzero(live) if len(K) else (np.zeros(0, dtype=np.int64),) * 2  # (t, j) ascending
+        ids, back = np.unique(track_id[r, j][::-1], return_index=True)  # the first from the back: the last row
+        r, j = r[::-1][back], j[::-1][back]
+        a = age[r, j].astype(np.int64)
+        last_frame = np.asarray(frames, dtype=np.int64)[r]
+        d = people[r, j] - origin[r, j]
+        path_length = path[r, j].astype(np.float64)
+        speed = np.zeros(len(ids), dtype=np.float64)
+        moving = a > 0
+        speed[moving] = path_length[moving] / (a[moving] * np.float64(dt))
+        return {"track_id": ids.astype(np.int32), "first_frame": last_frame - a, "last_frame": last_frame,
+                "hits": hits[r, j].astype(np.int32), "path_length": path_length,
+                "displacement": np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]), "mean_speed": speed}
+
+    @classmethod
+    def _history_keys(cls, K, frames, track_id, people, hist, dwell_total, dt):
+        """The history keys of analyze_sequence / analyze_stream from host copies: track_history's age, hits, path,
+        origin and stay (None without zones) over the frames K, numbered `frames`, and dwell_total (Z, 3) or None."""
+        age, hits, path, origin, stay = hist
+        rows = range(len(K))
+        out = {"ages": [age[t, :K[t]] for t in rows], "hits": [hits[t, :K[t]] for t in rows],
+               "path_lengths": [path[t, :K[t]] for t in rows], "origins": [origin[t, :K[t]] for t in rows],
+               "track_table": cls.track_table(track_id, age, hits, path, origin, people, K, frames, dt)}
+        if dwell_total is not None:
+            count, total = dwell_total[:, 0].astype(np.int64), dwell_total[:, 1].astype(np.int64)
+            with np.errstate(all="ignore"):
+                mean = np.where(count > 0, np.float64(dt) * total / count, np.nan)
+            out.update({"zone_stays": [stay[t, :K[t]] for t in rows], "zone_dwell_count": count,
+                        "zone_dwell_frames": total, "zone_dwell_max": dwell_total[:, 2].astype(np.int64),
+                        "zone_dwell_mean_s": mean})
+        return out
+
     def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
-                         min_observations=1, max_gap=0, gates=None, zones=None):
+                         min_observations=1, max_gap=0, gates=None, zones=None, history=False):
         """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
 
         people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
@@ -96,7 +137,16 @@ class CrowdFlowModel:
         and backward crossings (forward: from the right of A -> B to its left); gate_series (T, G, 2) int32 per
         frame; zone_occupancy (T, Z) int32; zone_entries / zone_exits (Z,) int64; gate_events {"forward",
         "backward"} and zone_membership: per frame (K_t,) int64, bit g / z set for the gates the row crossed
-        and the zones that hold it.  An absent kind has G or Z = 0 and zero masks."""
+        and the zones that hold it.  An absent kind has G or Z = 0 and zero masks.
+
+        history=True adds every track's history (``people_tracking.track_history``, DESIGN.md §3 "Track history"),
+        in the same read-back: ages and hits, per frame (K_t,) int32 (frames since the track's first detection,
+        detections so far); path_lengths per frame (K_t,) float64 and origins per frame (K_t, 2) (metres walked,
+        the first detection's position); track_table, ``track_table``'s dict with one entry per track, ids
+        0 .. tracks - 1, frames counted from 0.  With zones also zone_stays, per frame (K_t, Z) int32 (frames since
+        the row's present stay in the zone began, -1 outside); zone_dwell_count, zone_dwell_frames and
+        zone_dwell_max (Z,) int64 (the completed stays, their summed and largest length in frames) and
+        zone_dwell_mean_s (Z,) float64 = dt * frames / count, NaN without a completed stay."""
         import torch
         from . import people_tracking as pt
 
@@ -145,11 +195,13 @@ class CrowdFlowModel:
             prev, gap, _, velocity, track_id, ntracks = pt.track_stream(people, k, dt, gate, max_gap)
         count, vsum, _ = pt.flow_cells(people, k, prev, velocity, x_range, y_range, grid_size)
         dev = [k, prev, track_id, velocity, ntracks, count, vsum] + ([] if gap is None else [gap])
-        events = ()
+        events, hist, tables = (), (), [None, None]
         if gates is not None or zones is not None:
             tables = [None if t is None else torch.from_numpy(t).to(people.device) for t in (gates, zones)]
             events = pt.track_events(people, k, prev, gap, *tables)
-        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + list(events)]
+        if history:
+            hist = (people,) + pt.track_history(people, k, prev, gap, tables[1])
+        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + list(events) + list(hist)]
         torch.cuda.current_stream(people.device).synchronize()  # the one read-back
         kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host[:7])
         K = np.minimum(np.maximum(kh, 0), people.shape[1])
@@ -160,8 +212,13 @@ class CrowdFlowModel:
             gap = host[7].numpy()
             extras["gaps"] = [gap[t, :K[t]] for t in range(len(K))]
         if events:
-            ev = [None if t is None else t.numpy() for t in host[len(dev):]]
+            ev = [None if t is None else t.numpy() for t in host[len(dev):len(dev) + len(events)]]
             extras.update(self._event_keys(K, ev[0].sum(axis=0), ev[1][:, :, 1:].sum(axis=0), ev))
+        if history:
+            hp, *hs, dwell = (None if t is None else t.numpy() for t in host[len(dev) + len(events):])
+            total = None if dwell is None else np.concatenate(
+                [dwell[:, :, :2].sum(axis=0), dwell[:, :, 2].max(axis=0, initial=0)[:, None]], axis=1)
+            extras.update(self._history_keys(K, np.arange(len(K)), track_id, hp, hs, total, dt))
         return self._measured_flow(count, vsum, x_range, y_range, grid_size, min_observations, extras)
 
     def analyze_stream(self, tracker, min_observations=1):
@@ -171,7 +228,10 @@ class CrowdFlowModel:
         the frames the tracker still holds, its last min(max_gap + 1, frames) ones (the rows of earlier frames
         were returned by ``push``).  A tracker built with gates / zones adds ``analyze_sequence``'s gate and zone
         keys, in the same read-back: gate_counts, zone_entries and zone_exits total the whole stream;
-        gate_series, zone_occupancy, gate_events and zone_membership cover the held frames."""
+        gate_series, zone_occupancy, gate_events and zone_membership cover the held frames.  A tracker built with
+        history=True adds ``analyze_sequence``'s history keys, in the same read-back: the per-frame lists cover the
+        held frames, track_table the tracks present in them (frames counted from the first pushed frame), and the
+        zone_dwell keys total the whole stream."""
         import torch
 
         if int(min_observations) != min_observations or min_observations < 1:
@@ -185,11 +245,18 @@ class CrowdFlowModel:
                 none = (np.zeros((0, G, 2), dtype=np.int32), np.zeros((0, Z, 3), dtype=np.int32), None, None, None)
                 extras.update(self._event_keys([], np.zeros((G, 2), dtype=np.int64), np.zeros((Z, 2), dtype=np.int64),
                                                none))
+            if tracker.history:
+                Z = 0 if tracker._tables[1] is None else tracker._tables[1].shape[0]
+                none = (np.zeros((0, 1), dtype=np.int32), np.zeros((0, 1), dtype=np.int32), np.zeros((0, 1)),
+                        np.zeros((0, 1, 2)), np.zeros((0, 1, Z), dtype=np.int32))
+                extras.update(self._history_keys([], [], none[0], none[3], none,
+                                                 np.zeros((Z, 3), dtype=np.int64) if Z else None, tracker.dt))
             return self._measured_flow(None, None, None, None, None, min_observations, extras)
-        _, k, _, gap, _, velocity, track_id = tracker._carry
+        people, k, _, gap, _, velocity, track_id = tracker._carry
         dev = [k, gap, velocity, track_id, tracker.ntracks, tracker.matched, tracker.count, tracker.vsum]
         events = [tracker.gate_total, tracker.zone_total, *tracker._held_events] if tracker.events else []
-        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + events]
+        hist = [people, *tracker._held_history, tracker.dwell_total] if tracker.history else []
+        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + events + hist]
         torch.cuda.current_stream(k.device).synchronize()  # the one read-back
         kh, gap, velocity, track_id, ntracks, matched, count, vsum = (t.numpy() for t in host[:8])
         K = np.minimum(np.maximum(kh, 0), tracker.cap)
@@ -198,8 +265,13 @@ class CrowdFlowModel:
                   "velocities": [velocity[t, :K[t]] for t in range(len(K))],
                   "gaps": [gap[t, :K[t]] for t in range(len(K))]}
         if events:
-            ev = [None if t is None else t.numpy() for t in host[8:]]
+            ev = [None if t is None else t.numpy() for t in host[8:8 + len(events)]]
             extras.update(self._event_keys(K, ev[0], ev[1], ev[2:]))
+        if hist:
+            hp, *hs, total = (None if t is None else t.numpy() for t in host[8 + len(events):])
+            hs = hs + [None] * (5 - len(hs))  # no stay without zones
+            extras.update(self._history_keys(K, np.arange(tracker.frames - len(K), tracker.frames), track_id, hp, hs,
+                                             total, tracker.dt))
         return self._measured_flow(count, vsum, tracker.x_range, tracker.y_range, tracker.grid_size, min_observations,
                                    extras)
 

@@ -14,6 +14,10 @@ its ids last across ``push`` calls and a track survives up to ``max_gap`` frames
 crossings of gate lines, forward and backward, and occupancy, entries and exits of zones, per frame, with a bit
 mask per row; ``check_gates`` / ``check_zones`` validate a user's tables on the host, and
 ``PeopleTracker(gates=, zones=)`` totals the counts across ``push`` calls.
+
+``track_history`` (csrc/track_history.hip; DESIGN.md §3 "Track history", §4.13) follows the links forward: per
+detection the age, the hits, the path length and the origin of its track and how long it has been in each zone, per
+frame and zone the stays that ended; ``PeopleTracker(history=True)`` carries that state across ``push`` calls.
 """
 import math
 
@@ -237,6 +241,65 @@ def track_events(people, k, prev, gap=None, gates=None, zones=None, first=0, out
                  *(nat.ptr(t) if t is not None and t.numel() else None for t in out), nat.stream_ptr())
     return out
 
+# ------------------------------------------------------------------ track history
+HISTORY = (("age", torch.int32, ()), ("hits", torch.int32, ()), ("path", torch.float64, ()),
+           ("origin", torch.float64, (2,)))
+
+
+def _history_shapes(T, cap, Z):
+    """(name, dtype, shape) of track_history's state arrays: HISTORY's four, and stay with zones."""
+    return tuple((name, dtype, (T, cap) + tail) for name, dtype, tail in HISTORY) + (
+        (("stay", torch.int32, (T, cap, Z)),) if Z else ())
+
+
+def track_history(people, k, prev, gap=None, zones=None, carry=0, state=None, slot=0):
+    """Age, hits, path length, origin and zone dwell of every tracked detection, from the links (prev, gap)
+    track_people / track_stream left on the device (lidar_track_history_f64; DESIGN.md §3 "Track history").
+    people (T, cap, 2), k (T,), prev (T, cap) int32; gap (T, cap) int32, or None for track_people's prev (every link
+    spans one frame); zones (Z, 4) float64 device tensor, 1 .. 64 rows as track_events takes it, or None; the first
+    `carry` (0 .. T) frames' history is given in `state` = (age, hits, path, origin), or (age, hits, path, origin,
+    stay) with zones, each with T frames: (T, cap) int32, (T, cap) int32, (T, cap) float64, (T, cap, 2) float64,
+    (T, cap, Z) int32; the call fills the other frames in place.  Without a state (carry 0) they are allocated.
+    -> (age, hits, path, origin, stay, dwell (T - carry, Z, 3) int64: the stays that ended in each frame, their
+    number, their summed and their largest length in frames), device tensors, nothing synchronised; stay and dwell
+    are None without zones.  T == carry: no native call, nothing is written."""
+    what = "track_history"
+    T, cap = _check_people(what, people, k)
+    dev = people.device
+    _check_tensor(what, "prev", prev, dev, torch.int32, (T, cap))
+    if gap is not None:
+        _check_tensor(what, "gap", gap, dev, torch.int32, (T, cap))
+    Z = 0
+    if zones is not None:
+        _check_tensor(what, "zones", zones, dev)
+        if (zones.dtype != torch.float64 or zones.dim() != 2 or zones.shape[1] != 4
+                or not 1 <= zones.shape[0] <= MAX_TABLE):
+            raise ValueError(f"{what}: zones must be (n, 4) float64 with 1 <= n <= {MAX_TABLE}, got {zones.dtype} "
+                             f"{tuple(zones.shape)}")
+        Z = zones.shape[0]
+    if int(carry) != carry or not 0 <= carry <= T:
+        raise ValueError(f"{what}: carry must be an integer in 0 .. T = {T}, got {carry}")
+    carry = int(carry)
+    shapes = _history_shapes(T, cap, Z)
+    if state is None:
+        if carry:
+            raise ValueError(f"{what}: carried frames need their state")
+        state = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in shapes)
+    state = tuple(state)
+    if len(state) != len(shapes):
+        raise ValueError(f"{what}: state is (age, hits, path, origin"
+                         + (", stay) with zones" if Z else ") without zones"))
+    for t, (name, dtype, shape) in zip(state, shapes):
+        _check_tensor(what, name, t, dev, dtype, shape)
+    age, hits, path, origin = state[:4]
+    stay = state[4] if Z else None
+    dwell = torch.empty((T - carry, Z, 3), dtype=torch.int64, device=dev) if Z else None
+    if T > carry:  # an empty tensor has no address to pass
+        nat.call("lidar_track_history_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
+                 nat.ptr(gap), T, cap, carry, nat.ptr(zones), Z, nat.ptr(age), nat.ptr(hits), nat.ptr(path),
+                 nat.ptr(origin), nat.ptr(stay), nat.ptr(dwell), nat.stream_ptr())
+    return age, hits, path, origin, stay, dwell
+
 
 class PeopleTracker:
     """A sensor's people tracked batch after batch: ids that last across push() calls, tracks stitched over up
@@ -257,10 +320,18 @@ class PeopleTracker:
     exits), device tensors (G or Z = 0 for an absent kind; occupancy is per frame and not accumulated).
     last_events: track_events' five arrays for the frames of the last push.  However the stream is cut into
     pushes, the concatenated last_events and the totals are those of one call over the whole stream.  Without
-    gates and zones the three stay None and push makes no further call."""
+    gates and zones the three stay None and push makes no further call.
+
+    history=True: push also calls lidar_track_history_f64(carry = the held frames) after the tracking call, with the
+    zones table if one was given, and keeps the history arrays of the held frames beside the association state.
+    last_history: track_history's six outputs (age, hits, path, origin, stay, dwell) for the frames of the last push
+    (stay and dwell None without zones); dwell_total (Z, 3) int64, with zones: the completed stays of the whole
+    stream, their number and summed length added and their largest length maximised across pushes.  However the
+    stream is cut, the concatenated last_history and dwell_total are those of one call over the whole stream.
+    Without history the two stay None, and push makes exactly the calls it makes without the keyword."""
 
     def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0, gates=None,
-                 zones=None):
+                 zones=None, history=False):
         self.dt, self.gate = _positive("PeopleTracker", "dt", dt), _positive("PeopleTracker", "gate", gate)
         self.max_gap = _max_gap("PeopleTracker", max_gap)
         if (x_range is None) != (y_range is None):
@@ -278,6 +349,9 @@ class PeopleTracker:
         self.events = any(t is not None for t in self._tables)
         self.gate_total = self.zone_total = self.last_events = None
         self._held_events = None  # track_events' arrays of the frames in _carry
+        self.history = bool(history)
+        self.last_history = self.dwell_total = None
+        self._held_history = None  # track_history's state (age, hits, path, origin[, stay]) of the frames in _carry
 
     def push(self, people, k):
         """-> (prev, gap, track_id, velocity) of the T new frames, device tensors."""
@@ -300,6 +374,12 @@ class PeopleTracker:
                 self.zone_total = torch.zeros((Z, 2), dtype=torch.int64, device=dev)
                 self._held_events = tuple(None if shape is None else torch.empty(shape, dtype=dtype, device=dev)
                                           for _, dtype, shape in _event_shapes(0, cap, G, Z))
+            if self.history:
+                Z = 0 if self._tables[1] is None else self._tables[1].shape[0]  # a zones table was uploaded above
+                self._held_history = tuple(torch.empty(shape, dtype=dtype, device=dev)
+                                           for _, dtype, shape in _history_shapes(0, cap, Z))
+                if Z:
+                    self.dwell_total = torch.zeros((Z, 3), dtype=torch.int64, device=dev)
         if cap != self.cap or dev != self.ntracks.device:
             raise ValueError(f"PeopleTracker.push: cap and device are fixed by the first push ({self.cap}, "
                              f"{self.ntracks.device}), got {cap}, {dev}")
@@ -309,6 +389,10 @@ class PeopleTracker:
         if T == 0:
             if self.events:
                 self.last_events = tuple(None if t is None else t[C:] for t in self._held_events)
+            if self.history:
+                Z = 0 if self._tables[1] is None else self._tables[1].shape[0]
+                self.last_history = tuple(t[C:] for t in self._held_history) + (
+                    (torch.empty((0, Z, 3), dtype=torch.int64, device=dev),) if Z else (None, None))
             return tuple(self._carry[i][C:] for i in (2, 3, 6, 5))
         people = torch.cat([self._carry[0], people])
         k = torch.cat([self._carry[1], k])
@@ -328,5 +412,14 @@ class PeopleTracker:
             self.zone_total += self.last_events[1][:, :, 1:].sum(dim=0, dtype=torch.int64)
             self._held_events = tuple(None if t is None else torch.cat([h, t])[C + T - keep:]
                                       for h, t in zip(self._held_events, self.last_events))
+        if self.history:
+            hstate = tuple(torch.cat([c, torch.empty((T,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev)])
+                           for c in self._held_history)
+            out = track_history(people, k, prev, gap, self._tables[1], C, hstate, self.slot)
+            self.last_history = tuple(None if t is None else t[C:] for t in out[:5]) + (out[5],)
+            if out[5] is not None:
+                self.dwell_total[:, :2] += out[5][:, :, :2].sum(dim=0)
+                self.dwell_total[:, 2] = torch.maximum(self.dwell_total[:, 2], out[5][:, :, 2].amax(dim=0))
+            self._held_history = tuple(t[C + T - keep:] for t in hstate)
         self._carry = tuple(t[C + T - keep:] for t in (people, k, prev, gap, succ, velocity, track_id))
         return prev[C:], gap[C:], track_id[C:], velocity[C:]
