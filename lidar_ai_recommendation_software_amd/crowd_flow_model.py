@@ -21,6 +21,15 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _read_back(named, device):
+    """name -> device tensor or None  ->  name -> host ndarray, the None entries left out: every copy queued, then
+    the one synchronise of analyze_sequence / analyze_stream."""
+    import torch
+    host = {name: t.to("cpu", non_blocking=True) for name, t in named.items() if t is not None}
+    torch.cuda.current_stream(device).synchronize()
+    return {name: t.numpy() for name, t in host.items()}
+
+
 class CrowdFlowModel:
     """``models/crowd_flow_model.py:6-279``: same attributes, methods and outputs."""
 
@@ -51,20 +60,31 @@ class CrowdFlowModel:
                 "dominant_direction": dominant_direction, "bottlenecks": bottlenecks}
 
     @staticmethod
-    def _event_keys(K, gate_total, zone_total, events):
+    def _track_keys(K, host, matched):
+        """tracks, matched and the per-frame lists of both analyses over the frames K, from the host copies in `host`."""
+        rows = range(len(K))
+        out = {"tracks": int(host["ntracks"]), "matched": matched,
+               "track_ids": [host["track_id"][t, :K[t]] for t in rows],
+               "velocities": [host["velocity"][t, :K[t]] for t in rows]}
+        if "gap" in host:
+            out["gaps"] = [host["gap"][t, :K[t]] for t in rows]
+        return out
+
+    @staticmethod
+    def _event_keys(K, host, gate_total, zone_total):
         """The gate and zone keys of analyze_sequence / analyze_stream from the host copies of the totals
-        (G, 2) and (Z, 2) and of track_events' five arrays over the frames K (a mask None: that kind is absent)."""
-        gate_counts, zone_counts, gate_fwd, gate_bwd, zone_in = events
+        (G, 2) and (Z, 2) and, in `host` under track_events' names, of its arrays over the frames K (a mask that
+        is missing: that kind is absent)."""
         rows = range(len(K))
 
-        def sliced(mask):
-            return [np.zeros(K[t], dtype=np.int64) if mask is None else mask[t, :K[t]] for t in rows]
+        def sliced(name):
+            return [np.zeros(K[t], dtype=np.int64) if name not in host else host[name][t, :K[t]] for t in rows]
 
-        return {"gate_counts": gate_total.astype(np.int64), "gate_series": gate_counts,
-                "zone_occupancy": zone_counts[:, :, 0], "zone_entries": zone_total[:, 0].astype(np.int64),
+        return {"gate_counts": gate_total.astype(np.int64), "gate_series": host["gate_counts"],
+                "zone_occupancy": host["zone_counts"][:, :, 0], "zone_entries": zone_total[:, 0].astype(np.int64),
                 "zone_exits": zone_total[:, 1].astype(np.int64),
-                "gate_events": {"forward": sliced(gate_fwd), "backward": sliced(gate_bwd)},
-                "zone_membership": sliced(zone_in)}
+                "gate_events": {"forward": sliced("gate_fwd"), "backward": sliced("gate_bwd")},
+                "zone_membership": sliced("zone_in")}
 
     @staticmethod
     def track_table(track_id, age, hits, path, origin, people, K, frames, dt):
@@ -90,19 +110,21 @@ class CrowdFlowModel:
                 "displacement": np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]), "mean_speed": speed}
 
     @classmethod
-    def _history_keys(cls, K, frames, track_id, people, hist, dwell_total, dt):
-        """The history keys of analyze_sequence / analyze_stream from host copies: track_history's age, hits, path,
-        origin and stay (None without zones) over the frames K, numbered `frames`, and dwell_total (Z, 3) or None."""
-        age, hits, path, origin, stay = hist
+    def _history_keys(cls, K, frames, host, dwell_total, dt):
+        """The history keys of analyze_sequence / analyze_stream from host copies: in `host`, under their names,
+        people, track_id and track_history's age, hits, path, origin and (with zones) stay over the frames K,
+        numbered `frames`; dwell_total (Z, 3) or None."""
+        age, hits, path, origin = (host[name] for name in ("age", "hits", "path", "origin"))
         rows = range(len(K))
         out = {"ages": [age[t, :K[t]] for t in rows], "hits": [hits[t, :K[t]] for t in rows],
                "path_lengths": [path[t, :K[t]] for t in rows], "origins": [origin[t, :K[t]] for t in rows],
-               "track_table": cls.track_table(track_id, age, hits, path, origin, people, K, frames, dt)}
+               "track_table": cls.track_table(host["track_id"], age, hits, path, origin, host["people"], K, frames,
+                                              dt)}
         if dwell_total is not None:
             count, total = dwell_total[:, 0].astype(np.int64), dwell_total[:, 1].astype(np.int64)
             with np.errstate(all="ignore"):
                 mean = np.where(count > 0, np.float64(dt) * total / count, np.nan)
-            out.update({"zone_stays": [stay[t, :K[t]] for t in rows], "zone_dwell_count": count,
+            out.update({"zone_stays": [host["stay"][t, :K[t]] for t in rows], "zone_dwell_count": count,
                         "zone_dwell_frames": total, "zone_dwell_max": dwell_total[:, 2].astype(np.int64),
                         "zone_dwell_mean_s": mean})
         return out
@@ -150,26 +172,20 @@ class CrowdFlowModel:
         import torch
         from . import people_tracking as pt
 
-        def positive(name, v):
-            v = float(v)
-            if not (v > 0.0 and np.isfinite(v)):
-                raise ValueError(f"analyze_sequence: {name} must be positive and finite, got {v}")
-            return v
-
         def extent(name, r):
             r = tuple(float(v) for v in r)
             if len(r) != 2 or not np.all(np.isfinite(r)) or r[0] > r[1]:
                 raise ValueError(f"analyze_sequence: {name} must be a finite (min, max) with min <= max, got {r}")
             return r
 
-        dt = positive("dt", dt)
-        gate = positive("gate", float(max_speed) * dt if gate is None else gate)
-        grid_size = positive("grid_size", grid_size)
+        what = "analyze_sequence"  # people_tracking's checks and messages, under this name
+        dt = pt._positive(what, "dt", dt)
+        gate = pt._positive(what, "gate", float(max_speed) * dt if gate is None else gate)
+        grid_size = pt._positive(what, "grid_size", grid_size)
         x_range, y_range = extent("x_range", x_range), extent("y_range", y_range)
         if int(min_observations) != min_observations or min_observations < 1:
             raise ValueError(f"analyze_sequence: min_observations must be an integer >= 1, got {min_observations}")
-        if int(max_gap) != max_gap or not 0 <= max_gap <= pt.MAX_GAP:
-            raise ValueError(f"analyze_sequence: max_gap must be an integer in 0 .. {pt.MAX_GAP}, got {max_gap}")
+        max_gap = pt._integer(what, "max_gap", max_gap, pt.MAX_GAP)
         gates = None if gates is None else pt.check_gates(gates)
         zones = None if zones is None else pt.check_zones(zones)
         if isinstance(people, torch.Tensor):
@@ -194,32 +210,28 @@ class CrowdFlowModel:
         else:
             prev, gap, _, velocity, track_id, ntracks = pt.track_stream(people, k, dt, gate, max_gap)
         count, vsum, _ = pt.flow_cells(people, k, prev, velocity, x_range, y_range, grid_size)
-        dev = [k, prev, track_id, velocity, ntracks, count, vsum] + ([] if gap is None else [gap])
-        events, hist, tables = (), (), [None, None]
+        named = {"k": k, "prev": prev, "gap": gap, "track_id": track_id, "velocity": velocity, "ntracks": ntracks,
+                 "count": count, "vsum": vsum}
+        tables = [None, None]
         if gates is not None or zones is not None:
             tables = [None if t is None else torch.from_numpy(t).to(people.device) for t in (gates, zones)]
-            events = pt.track_events(people, k, prev, gap, *tables)
+            named.update(zip(pt.EVENTS, pt.track_events(people, k, prev, gap, *tables)))
         if history:
-            hist = (people,) + pt.track_history(people, k, prev, gap, tables[1])
-        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + list(events) + list(hist)]
-        torch.cuda.current_stream(people.device).synchronize()  # the one read-back
-        kh, prev, track_id, velocity, ntracks, count, vsum = (t.numpy() for t in host[:7])
-        K = np.minimum(np.maximum(kh, 0), people.shape[1])
-        extras = {"tracks": int(ntracks), "matched": int(np.sum(prev >= 0)),
-                  "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
-                  "velocities": [velocity[t, :K[t]] for t in range(len(K))]}
-        if gap is not None:
-            gap = host[7].numpy()
-            extras["gaps"] = [gap[t, :K[t]] for t in range(len(K))]
-        if events:
-            ev = [None if t is None else t.numpy() for t in host[len(dev):len(dev) + len(events)]]
-            extras.update(self._event_keys(K, ev[0].sum(axis=0), ev[1][:, :, 1:].sum(axis=0), ev))
+            named["people"] = people
+            named.update(zip([name for name, _, _ in pt.HISTORY] + ["stay", "dwell"],
+                             pt.track_history(people, k, prev, gap, tables[1])))
+        host = _read_back(named, people.device)  # the one read-back
+        K = np.minimum(np.maximum(host["k"], 0), people.shape[1])
+        extras = self._track_keys(K, host, int(np.sum(host["prev"] >= 0)))
+        if "gate_counts" in host:
+            extras.update(self._event_keys(K, host, host["gate_counts"].sum(axis=0),
+                                           host["zone_counts"][:, :, 1:].sum(axis=0)))
         if history:
-            hp, *hs, dwell = (None if t is None else t.numpy() for t in host[len(dev) + len(events):])
+            dwell = host.get("dwell")
             total = None if dwell is None else np.concatenate(
                 [dwell[:, :, :2].sum(axis=0), dwell[:, :, 2].max(axis=0, initial=0)[:, None]], axis=1)
-            extras.update(self._history_keys(K, np.arange(len(K)), track_id, hp, hs, total, dt))
-        return self._measured_flow(count, vsum, x_range, y_range, grid_size, min_observations, extras)
+            extras.update(self._history_keys(K, np.arange(len(K)), host, total, dt))
+        return self._measured_flow(host["count"], host["vsum"], x_range, y_range, grid_size, min_observations, extras)
 
     def analyze_stream(self, tracker, min_observations=1):
         """Measured flow of everything pushed into a ``people_tracking.PeopleTracker`` that was given a venue
@@ -238,42 +250,29 @@ class CrowdFlowModel:
             raise ValueError(f"analyze_stream: min_observations must be an integer >= 1, got {min_observations}")
         if tracker.grid is None:
             raise ValueError("analyze_stream: the tracker was built without x_range / y_range: it holds no flow cells")
-        if tracker.frames == 0:
-            extras = {"tracks": 0, "matched": 0, "track_ids": [], "velocities": [], "gaps": []}
-            if tracker.events:
-                G, Z = (0 if t is None else t.shape[0] for t in tracker._tables)
-                none = (np.zeros((0, G, 2), dtype=np.int32), np.zeros((0, Z, 3), dtype=np.int32), None, None, None)
-                extras.update(self._event_keys([], np.zeros((G, 2), dtype=np.int64), np.zeros((Z, 2), dtype=np.int64),
-                                               none))
-            if tracker.history:
-                Z = 0 if tracker._tables[1] is None else tracker._tables[1].shape[0]
-                none = (np.zeros((0, 1), dtype=np.int32), np.zeros((0, 1), dtype=np.int32), np.zeros((0, 1)),
-                        np.zeros((0, 1, 2)), np.zeros((0, 1, Z), dtype=np.int32))
-                extras.update(self._history_keys([], [], none[0], none[3], none,
-                                                 np.zeros((Z, 3), dtype=np.int64) if Z else None, tracker.dt))
-            return self._measured_flow(None, None, None, None, None, min_observations, extras)
-        people, k, _, gap, _, velocity, track_id = tracker._carry
-        dev = [k, gap, velocity, track_id, tracker.ntracks, tracker.matched, tracker.count, tracker.vsum]
-        events = [tracker.gate_total, tracker.zone_total, *tracker._held_events] if tracker.events else []
-        hist = [people, *tracker._held_history, tracker.dwell_total] if tracker.history else []
-        host = [None if t is None else t.to("cpu", non_blocking=True) for t in dev + events + hist]
-        torch.cuda.current_stream(k.device).synchronize()  # the one read-back
-        kh, gap, velocity, track_id, ntracks, matched, count, vsum = (t.numpy() for t in host[:8])
-        K = np.minimum(np.maximum(kh, 0), tracker.cap)
-        extras = {"tracks": int(ntracks), "matched": int(matched),
-                  "track_ids": [track_id[t, :K[t]] for t in range(len(K))],
-                  "velocities": [velocity[t, :K[t]] for t in range(len(K))],
-                  "gaps": [gap[t, :K[t]] for t in range(len(K))]}
-        if events:
-            ev = [None if t is None else t.numpy() for t in host[8:8 + len(events)]]
-            extras.update(self._event_keys(K, ev[0], ev[1], ev[2:]))
-        if hist:
-            hp, *hs, total = (None if t is None else t.numpy() for t in host[8 + len(events):])
-            hs = hs + [None] * (5 - len(hs))  # no stay without zones
-            extras.update(self._history_keys(K, np.arange(tracker.frames - len(K), tracker.frames), track_id, hp, hs,
-                                             total, tracker.dt))
-        return self._measured_flow(count, vsum, tracker.x_range, tracker.y_range, tracker.grid_size, min_observations,
-                                   extras)
+        if tracker.frames == 0:  # nothing to read back: the held arrays without a frame, and zero totals
+            host = {name: torch.empty(shape, dtype=dtype).numpy() for name, dtype, shape in tracker.layout(0)}
+            host.update(ntracks=0, matched=0, gate_total=np.zeros((tracker.G, 2), dtype=np.int64),
+                        zone_total=np.zeros((tracker.Z, 2), dtype=np.int64))
+            if tracker.history and tracker.Z:
+                host["dwell_total"] = np.zeros((tracker.Z, 3), dtype=np.int64)
+        else:
+            held = tracker.held()
+            for name in ("prev", "succ") + (() if tracker.history else ("people",)):
+                del held[name]  # no key needs them (the positions: only the history keys)
+            host = _read_back({**held, "ntracks": tracker.ntracks, "matched": tracker.matched, "count": tracker.count,
+                               "vsum": tracker.vsum, "gate_total": tracker.gate_total,
+                               "zone_total": tracker.zone_total, "dwell_total": tracker.dwell_total},
+                              tracker.ntracks.device)  # the one read-back
+        K = np.minimum(np.maximum(host["k"], 0), tracker.cap or 1)
+        extras = self._track_keys(K, host, int(host["matched"]))
+        if tracker.events:
+            extras.update(self._event_keys(K, host, host["gate_total"], host["zone_total"]))
+        if tracker.history:
+            extras.update(self._history_keys(K, np.arange(tracker.frames - len(K), tracker.frames), host,
+                                             host.get("dwell_total"), tracker.dt))
+        return self._measured_flow(host.get("count"), host.get("vsum"), tracker.x_range, tracker.y_range,
+                                   tracker.grid_size, min_observations, extras)
 
     def _measured_flow(self, count, vsum, x_range, y_range, grid_size, min_observations, extras):
         """analyze's keys from the flow cells (count, vsum) on the host."""

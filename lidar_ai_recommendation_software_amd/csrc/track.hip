@@ -34,23 +34,18 @@
 // detections streamed through LDS in (t, j) order and handed to the cell's thread one after the other).
 #include <cmath>
 
-#include "tier_r.hpp"
+#include "track_links.hpp"
 
 namespace {
 
 using namespace lidar::tier_r;
+using namespace lidar::track;
 
 constexpr int kB = 256;                // threads of nearest_kernel and the per-detection kernels
 constexpr int kTile = 2048;            // rows of the other frame staged in LDS (16 B each: 32 KiB)
 constexpr int kRounds = kTile / kB;    // staging rounds of a tile in nearest_kernel<Compact>: row r * kB + thread
 constexpr int kWaves = kB / 64;
 constexpr int kRec = 1024;             // detections per LDS tile of flow_accumulate_kernel
-
-__device__ __forceinline__ int64_t clamp_k(const int64_t *k, int64_t t, int64_t cap)
-{
-    const int64_t v = k[t];
-    return v < 0 ? 0 : (v < cap ? v : cap);
-}
 
 // The rows nearest_kernel takes.  An end row (frame u - g) is open while succ == 0, a start row (frame u)
 // while prev == -1.
@@ -455,10 +450,7 @@ inline unsigned flat_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, s
 int check_track(const char *fn, bool pointers, int64_t frames, int64_t cap, double dt, double gate)
 {
     const std::string f(fn);
-    REQUIRE(pointers, f + ": null pointer");
-    REQUIRE(frames >= 0 && frames <= 65535, f + ": frames out of range");
-    REQUIRE(cap >= 1, f + ": cap must be >= 1");
-    REQUIRE(cap < 0x80000000ll && frames * cap < 0x80000000ll, f + ": frames * cap must be below 2^31");
+    if (int rc = check_frames(f, pointers, frames, cap)) return rc;
     REQUIRE(pos_finite(dt), f + ": dt must be positive and finite");
     REQUIRE(pos_finite(gate), f + ": gate must be positive and finite");
     return LIDAR_OK;
@@ -537,7 +529,7 @@ LIDAR_EXPORT int lidar_track_stream_f64(lidar_handle *h, const double *people, c
                              h && people && k && prev && gap && succ && velocity && track_id && ntracks, frames, cap, dt,
                              gate))
         return rc;
-    REQUIRE(max_gap >= 0 && max_gap <= 7, "lidar_track_stream_f64: max_gap must be in 0 .. 7");
+    REQUIRE(max_gap >= 0 && max_gap + 1 <= kMaxGap, "lidar_track_stream_f64: max_gap must be in 0 .. 7");
     REQUIRE(carry >= 0 && carry <= std::min<int64_t>(max_gap + 1, frames),
             "lidar_track_stream_f64: carry must be in 0 .. min(max_gap + 1, frames)");
     if (frames == carry) return LIDAR_OK;  // no frame to link (frames == 0 among them): nothing is written
@@ -547,9 +539,10 @@ LIDAR_EXPORT int lidar_track_stream_f64(lidar_handle *h, const double *people, c
     TrackWs w;
     if (!carve_track(h, frames, cap, carry, true, w)) return LIDAR_ENOMEM;
 
-    static const char *const kPass[8] = {"track_stream_pass1", "track_stream_pass2", "track_stream_pass3",
-                                         "track_stream_pass4", "track_stream_pass5", "track_stream_pass6",
-                                         "track_stream_pass7", "track_stream_pass8"};
+    static const char *const kPass[] = {"track_stream_pass1", "track_stream_pass2", "track_stream_pass3",
+                                        "track_stream_pass4", "track_stream_pass5", "track_stream_pass6",
+                                        "track_stream_pass7", "track_stream_pass8"};
+    static_assert(sizeof(kPass) / sizeof(kPass[0]) == kMaxGap, "a span name per frame distance of a link");
     {
         lidar::Span sp(h, "track_stream_init", s);
         hipLaunchKernelGGL(init_stream_kernel, dim3(flat_blocks(w.nnew)), dim3(kB), 0, s, first, n, prev, gap, succ,
@@ -586,10 +579,7 @@ int flow_cells(const char *fn, lidar_handle *h, const double *people, const int6
                double grid, int64_t nx, int64_t ny, int32_t *count, double *vsum, void *stream)
 {
     const std::string f(fn);
-    REQUIRE(h && people && k && prev && velocity && count && vsum, f + ": null pointer");
-    REQUIRE(frames >= 0 && frames <= 65535, f + ": frames out of range");
-    REQUIRE(cap >= 1, f + ": cap must be >= 1");
-    REQUIRE(cap < 0x80000000ll && frames * cap < 0x80000000ll, f + ": frames * cap must be below 2^31");
+    if (int rc = check_frames(f, h && people && k && prev && velocity && count && vsum, frames, cap)) return rc;
     REQUIRE(first >= 0 && first <= frames, f + ": first must be in 0 .. frames");
     REQUIRE(accumulate == 0 || accumulate == 1, f + ": accumulate must be 0 or 1");
     REQUIRE(pos_finite(grid), f + ": grid must be positive and finite");

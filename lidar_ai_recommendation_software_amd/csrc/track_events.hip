@@ -26,22 +26,15 @@
 // stores its counters instead: no other workgroup adds to them, so that call needs no zero_counts_kernel before it.
 #include <cmath>
 
-#include "tier_r.hpp"
+#include "track_links.hpp"
 
 namespace {
 
 using namespace lidar::tier_r;
+using namespace lidar::track;
 
-constexpr int kB = 256;      // threads of events_kernel: one row each
-constexpr int kMaxTab = 64;  // gates, and zones, at most: a bit of an int64 mask each
-constexpr int kMaxGap = 8;   // the largest frame distance of a link (lidar_track_stream_f64: max_gap + 1 <= 8)
+constexpr int kB = 256;  // threads of events_kernel: one row each
 static_assert(4 * kMaxTab <= kB && 3 * kMaxTab <= kB, "a table is staged, and the counters are flushed, in one round");
-
-__device__ __forceinline__ int64_t clamp_k(const int64_t *k, int64_t t, int64_t cap)
-{
-    const int64_t v = k[t];
-    return v < 0 ? 0 : (v < cap ? v : cap);
-}
 
 __device__ __forceinline__ double side(double ax, double ay, double bx, double by, double px, double py)
 {
@@ -98,10 +91,10 @@ __global__ __launch_bounds__(kB) void events_kernel(const double *__restrict__ p
         if (live) {
             qx = people[2 * e];
             qy = people[2 * e + 1];
-            const int64_t i = prev[e], g = gap ? gap[e] : 1;
-            if (i >= 0 && g >= 1 && g <= kMaxGap && g <= t && i < clamp_k(k, t - g, cap)) {
+            int64_t g;
+            const int64_t a = source_of(k, prev, gap, cap, t, e, g);  // inside people, or -1
+            if (a >= 0) {
                 linked = true;
-                const int64_t a = (t - g) * cap + i;  // 0 <= t - g, i < K_(t-g) <= cap: inside people
                 px = people[2 * a];
                 py = people[2 * a + 1];
             }
@@ -126,8 +119,7 @@ __global__ __launch_bounds__(kB) void events_kernel(const double *__restrict__ p
         if (__ballot(live)) {
             for (int z = 0; z < Z; ++z) {
                 const double x0 = sz[4 * z], x1 = sz[4 * z + 1], y0 = sz[4 * z + 2], y1 = sz[4 * z + 3];
-                const bool inq = x0 <= qx && qx < x1 && y0 <= qy && qy < y1;
-                const bool inp = x0 <= px && px < x1 && y0 <= py && py < y1;
+                const bool inq = inside(x0, x1, y0, y1, qx, qy), inp = inside(x0, x1, y0, y1, px, py);
                 const bool in = linked && inq && !inp, out = linked && inp && !inq;
                 mz |= (uint64_t)inq << z;
                 const uint64_t bo = __ballot(inq), bi = __ballot(in), be = __ballot(out);
@@ -171,10 +163,7 @@ LIDAR_EXPORT int lidar_track_events_f64(lidar_handle *h, const double *people, c
                                         int64_t *zone_in, void *stream)
 {
     const std::string f("lidar_track_events_f64");
-    REQUIRE(h && people && k && prev, f + ": null pointer");
-    REQUIRE(frames >= 0 && frames <= 65535, f + ": frames out of range");
-    REQUIRE(cap >= 1, f + ": cap must be >= 1");
-    REQUIRE(cap < 0x80000000ll && frames * cap < 0x80000000ll, f + ": frames * cap must be below 2^31");
+    if (int rc = check_frames(f, h && people && k && prev, frames, cap)) return rc;
     REQUIRE(first >= 0 && first <= frames, f + ": first must be in 0 .. frames");
     REQUIRE(ngates >= 0 && ngates <= kMaxTab && nzones >= 0 && nzones <= kMaxTab,
             f + ": ngates and nzones must be in 0 .. 64");

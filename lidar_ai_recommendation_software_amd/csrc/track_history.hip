@@ -42,36 +42,17 @@
 //                  per zone and step: 3 times slower at 8 zones, 10 to 20 times at 64)
 #include <cmath>
 
-#include "tier_r.hpp"
+#include "track_links.hpp"
 
 namespace {
 
 using namespace lidar::tier_r;
+using namespace lidar::track;
 
 constexpr int kB = 256;              // threads per workgroup
 constexpr int kWaves = kB / 64;
-constexpr int kMaxTab = 64;          // zones at most (track_events.hip)
-constexpr int kMaxGap = 8;           // the largest frame distance of a link (track_events.hip)
 constexpr int32_t kNone = 0x7fffffff;  // above every row index: frames * cap < 2^31
 static_assert(kMaxTab <= 64, "a zone per lane");
-
-__device__ __forceinline__ int64_t clamp_k(const int64_t *k, int64_t t, int64_t cap)
-{
-    const int64_t v = k[t];
-    return v < 0 ? 0 : (v < cap ? v : cap);
-}
-
-// events_kernel's guard: the source row index of the live row e = (t, j), -1 for an unlinked one; g: the link's
-// frame distance.  0 <= t - g and i < K_(t-g) <= cap: the source is inside the arrays.
-__device__ __forceinline__ int64_t source_of(const int64_t *__restrict__ k, const int32_t *__restrict__ prev,
-                                             const int32_t *__restrict__ gap, int64_t cap, int64_t t, int64_t e,
-                                             int64_t &g)
-{
-    const int64_t i = prev[e];
-    g = gap ? gap[e] : 1;
-    if (i >= 0 && g >= 1 && g <= kMaxGap && g <= t && i < clamp_k(k, t - g, cap)) return (t - g) * cap + i;
-    return -1;
-}
 
 __global__ __launch_bounds__(kB) void init_kernel(int32_t *__restrict__ next, int64_t nn, int64_t *__restrict__ dwell,
                                                   int64_t nd)
@@ -231,7 +212,7 @@ __global__ __launch_bounds__(kB) void walk_zones_kernel(
         for (;;) {
             advance(h, cont, g, qx, qy);
             if (lane == 0) store_row(h, e, age, hits, path, origin);
-            const bool in = x0 <= qx && qx < x1 && y0 <= qy && qy < y1;  // false in a lane without a zone
+            const bool in = inside(x0, x1, y0, y1, qx, qy);  // false in a lane without a zone
             const int32_t was = cont ? st : -1;
             st = in ? (was >= 0 ? was + (int32_t)g : 0) : -1;
             if (mine) stay[e * Z + lane] = st;
@@ -265,10 +246,7 @@ LIDAR_EXPORT int lidar_track_history_f64(lidar_handle *h, const double *people, 
                                          double *origin, int32_t *stay, int64_t *dwell, void *stream)
 {
     const std::string f("lidar_track_history_f64");
-    REQUIRE(h && people && k && prev && age && hits && path && origin, f + ": null pointer");
-    REQUIRE(frames >= 0 && frames <= 65535, f + ": frames out of range");
-    REQUIRE(cap >= 1, f + ": cap must be >= 1");
-    REQUIRE(cap < 0x80000000ll && frames * cap < 0x80000000ll, f + ": frames * cap must be below 2^31");
+    if (int rc = check_frames(f, h && people && k && prev && age && hits && path && origin, frames, cap)) return rc;
     REQUIRE(carry >= 0 && carry <= frames, f + ": carry must be in 0 .. frames");
     REQUIRE(nzones >= 0 && nzones <= kMaxTab, f + ": nzones must be in 0 .. 64");
     REQUIRE(nzones == 0 || (zones && stay && dwell), f + ": null zone table or zone output");

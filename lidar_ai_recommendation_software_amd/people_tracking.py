@@ -46,6 +46,54 @@ def _check_people(what, people, k):
     return T, people.shape[1]
 
 
+def _check_links(what, people, prev, gap=None):
+    """prev, and gap if given, are (T, cap) int32 on people's device."""
+    _check_tensor(what, "prev", prev, people.device, torch.int32, tuple(people.shape[:2]))
+    if gap is not None:
+        _check_tensor(what, "gap", gap, people.device, torch.int32, tuple(people.shape[:2]))
+
+
+def _check_device_table(what, name, t, dev):
+    """A gate or zone table on people's device, (n, 4) float64 with 1 .. MAX_TABLE rows -> n; None (no table) -> 0."""
+    if t is None:
+        return 0
+    _check_tensor(what, name, t, dev)
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or not 1 <= t.shape[0] <= MAX_TABLE:
+        raise ValueError(f"{what}: {name} must be (n, 4) float64 with 1 <= n <= {MAX_TABLE}, got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    return t.shape[0]
+
+
+def _integer(what, name, v, hi, bound=""):
+    """v is an integer in 0 .. hi -> int(v); bound: how the message spells hi ("T = ")."""
+    if int(v) != v or not 0 <= v <= hi:
+        raise ValueError(f"{what}: {name} must be an integer in 0 .. {bound}{hi}, got {v}")
+    return int(v)
+
+
+def _take(what, which, given, layout, dev, note="", holes=False, carry=0):
+    """The caller's arrays `given` (its argument `which`) or, without them, fresh ones, each checked against its
+    (name, dtype, shape) row of the layout; a row with shape None (an absent kind) takes None only.  holes: a None
+    among the given ones is allocated too.  carry: the leading frames the arrays must bring with them."""
+    if given is None and carry:
+        raise ValueError(f"{what}: carried frames need their {which}")
+    fresh = holes or given is None
+    given = (None,) * len(layout) if given is None else tuple(given)
+    if len(given) != len(layout):
+        raise ValueError(f"{what}: {which} is ({', '.join(name for name, _, _ in layout)}){note}")
+    out = []
+    for t, (name, dtype, shape) in zip(given, layout):
+        if shape is None:
+            if t is not None:
+                raise ValueError(f"{what}: {which}'s {name} must be None without its table")
+        elif t is None and fresh:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        else:
+            _check_tensor(what, name, t, dev, dtype, shape)
+        out.append(t)
+    return tuple(out)
+
+
 def _flow_cells_acc(people, k, prev, velocity, first, accumulate, grid, grid_size, count, vsum, slot):
     """lidar_flow_cells_acc_f64 over checked tensors: the frames >= first into count / vsum, which it overwrites
     (accumulate = 0) or continues (1); first = 1, accumulate = 0 is lidar_flow_cells_f64."""
@@ -90,7 +138,7 @@ def flow_cells(people, k, prev, velocity, x_range, y_range, grid_size=1.0, slot=
     detection is binned by its own position with VenueGrid's binning; vsum adds the velocities of a cell's
     detections sequentially in (t, j) order, so it is the same bits on every run."""
     T, cap = _check_people("flow_cells", people, k)
-    _check_tensor("flow_cells", "prev", prev, people.device, torch.int32, (T, cap))
+    _check_links("flow_cells", people, prev)
     _check_tensor("flow_cells", "velocity", velocity, people.device, torch.float64, (T, cap, 2))
     g = _positive("flow_cells", "grid_size", grid_size)
     grid = venue_grid(x_range, y_range, g)  # (x0, y0, nx, ny)
@@ -108,10 +156,9 @@ STATE = (("prev", torch.int32, ()), ("gap", torch.int32, ()), ("succ", torch.uin
          ("velocity", torch.float64, (2,)), ("track_id", torch.int32, ()))
 
 
-def _max_gap(what, max_gap):
-    if int(max_gap) != max_gap or not 0 <= max_gap <= MAX_GAP:
-        raise ValueError(f"{what}: max_gap must be an integer in 0 .. {MAX_GAP}, got {max_gap}")
-    return int(max_gap)
+def state_layout(T, cap):
+    """(name, dtype, shape) of track_stream's five state arrays over T frames."""
+    return tuple((name, dtype, (T, cap) + tail) for name, dtype, tail in STATE)
 
 
 def track_stream(people, k, dt, gate, max_gap=0, carry=0, state=None, ntracks=None, slot=0):
@@ -125,32 +172,22 @@ def track_stream(people, k, dt, gate, max_gap=0, carry=0, state=None, ntracks=No
     tensors, nothing synchronised.  gap[t, j]: the predecessor of row j lives in frame t - gap (0: none)."""
     T, cap = _check_people("track_stream", people, k)
     dt, gate = _positive("track_stream", "dt", dt), _positive("track_stream", "gate", gate)
-    max_gap = _max_gap("track_stream", max_gap)
-    if int(carry) != carry or not 0 <= carry <= min(max_gap + 1, T):
-        raise ValueError(f"track_stream: carry must be an integer in 0 .. min(max_gap + 1, T) = "
-                         f"{min(max_gap + 1, T)}, got {carry}")
+    max_gap = _integer("track_stream", "max_gap", max_gap, MAX_GAP)
+    carry = _integer("track_stream", "carry", carry, min(max_gap + 1, T), "min(max_gap + 1, T) = ")
     dev = people.device
-    if state is None:
-        if carry:
-            raise ValueError("track_stream: carried frames need their state")
-        state = tuple(torch.empty((T, cap) + tail, dtype=dtype, device=dev) for _, dtype, tail in STATE)
-    if len(state) != len(STATE):
-        raise ValueError("track_stream: state is (prev, gap, succ, velocity, track_id)")
-    for t, (name, dtype, tail) in zip(state, STATE):
-        _check_tensor("track_stream", name, t, dev, dtype, (T, cap) + tail)
+    state = _take("track_stream", "state", state, state_layout(T, cap), dev, carry=carry)
     if ntracks is None:
         ntracks = torch.zeros((), dtype=torch.int64, device=dev)
     _check_tensor("track_stream", "ntracks", ntracks, dev, torch.int64, ())
     if T:
-        prev, gap, succ, velocity, track_id = state
-        nat.call("lidar_track_stream_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), T, cap, int(carry),
-                 dt, gate, max_gap, nat.ptr(prev), nat.ptr(gap), nat.ptr(succ), nat.ptr(velocity), nat.ptr(track_id),
-                 nat.ptr(ntracks), nat.stream_ptr())
+        nat.call("lidar_track_stream_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), T, cap, carry, dt,
+                 gate, max_gap, *(nat.ptr(t) for t in state), nat.ptr(ntracks), nat.stream_ptr())
     return (*state, ntracks)
 
 
 # ------------------------------------------------------------------ gate and zone events (DESIGN.md §4.12)
 MAX_TABLE = 64  # gates, and zones, per call: a bit of an int64 mask each
+EVENTS = ("gate_counts", "zone_counts", "gate_fwd", "gate_bwd", "zone_in")  # track_events' outputs, in order
 
 
 def _check_table(what, name, rows):
@@ -183,11 +220,11 @@ def check_zones(zones):
     return a
 
 
-def _event_shapes(nf, cap, G, Z):
-    """(name, dtype, shape) of track_events' five outputs; a mask of an absent kind is None."""
-    return (("gate_counts", torch.int32, (nf, G, 2)), ("zone_counts", torch.int32, (nf, Z, 3)),
-            ("gate_fwd", torch.int64, (nf, cap) if G else None), ("gate_bwd", torch.int64, (nf, cap) if G else None),
-            ("zone_in", torch.int64, (nf, cap) if Z else None))
+def event_layout(nf, cap, G, Z):
+    """(name, dtype, shape) of track_events' five outputs over nf frames; a mask of an absent kind has shape None."""
+    return tuple(zip(EVENTS, (torch.int32, torch.int32, torch.int64, torch.int64, torch.int64),
+                     ((nf, G, 2), (nf, Z, 3), (nf, cap) if G else None, (nf, cap) if G else None,
+                      (nf, cap) if Z else None)))
 
 
 def track_events(people, k, prev, gap=None, gates=None, zones=None, first=0, out=None, slot=0):
@@ -203,51 +240,26 @@ def track_events(people, k, prev, gap=None, gates=None, zones=None, first=0, out
     what = "track_events"
     T, cap = _check_people(what, people, k)
     dev = people.device
-    _check_tensor(what, "prev", prev, dev, torch.int32, (T, cap))
-    if gap is not None:
-        _check_tensor(what, "gap", gap, dev, torch.int32, (T, cap))
+    _check_links(what, people, prev, gap)
     if gates is None and zones is None:
         raise ValueError(f"{what}: needs gates or zones")
-    n = {}
-    for name, t in (("gates", gates), ("zones", zones)):
-        n[name] = 0
-        if t is not None:
-            _check_tensor(what, name, t, dev)
-            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 4 or not 1 <= t.shape[0] <= MAX_TABLE:
-                raise ValueError(f"{what}: {name} must be (n, 4) float64 with 1 <= n <= {MAX_TABLE}, got {t.dtype} "
-                                 f"{tuple(t.shape)}")
-            n[name] = t.shape[0]
-    if int(first) != first or not 0 <= first <= T:
-        raise ValueError(f"{what}: first must be an integer in 0 .. T = {T}, got {first}")
-    first = int(first)
-    shapes = _event_shapes(T - first, cap, n["gates"], n["zones"])
-    given = (None,) * len(shapes) if out is None else tuple(out)
-    if len(given) != len(shapes):
-        raise ValueError(f"{what}: out is (gate_counts, zone_counts, gate_fwd, gate_bwd, zone_in)")
-    out = []
-    for t, (name, dtype, shape) in zip(given, shapes):
-        if shape is None:
-            if t is not None:
-                raise ValueError(f"{what}: out's {name} must be None without its table")
-        elif t is None:  # a None among out is allocated like all of them without out
-            t = torch.empty(shape, dtype=dtype, device=dev)
-        else:
-            _check_tensor(what, name, t, dev, dtype, shape)
-        out.append(t)
-    out = tuple(out)
+    G, Z = _check_device_table(what, "gates", gates, dev), _check_device_table(what, "zones", zones, dev)
+    first = _integer(what, "first", first, T, "T = ")
+    out = _take(what, "out", out, event_layout(T - first, cap, G, Z), dev, holes=True)
     if T > first:  # an empty tensor has no address to pass
         nat.call("lidar_track_events_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
-                 nat.ptr(gap), T, cap, first, nat.ptr(gates), n["gates"], nat.ptr(zones), n["zones"],
+                 nat.ptr(gap), T, cap, first, nat.ptr(gates), G, nat.ptr(zones), Z,
                  *(nat.ptr(t) if t is not None and t.numel() else None for t in out), nat.stream_ptr())
     return out
+
 
 # ------------------------------------------------------------------ track history
 HISTORY = (("age", torch.int32, ()), ("hits", torch.int32, ()), ("path", torch.float64, ()),
            ("origin", torch.float64, (2,)))
 
 
-def _history_shapes(T, cap, Z):
-    """(name, dtype, shape) of track_history's state arrays: HISTORY's four, and stay with zones."""
+def history_layout(T, cap, Z):
+    """(name, dtype, shape) of track_history's state arrays over T frames: HISTORY's four, and stay with zones."""
     return tuple((name, dtype, (T, cap) + tail) for name, dtype, tail in HISTORY) + (
         (("stay", torch.int32, (T, cap, Z)),) if Z else ())
 
@@ -266,39 +278,17 @@ def track_history(people, k, prev, gap=None, zones=None, carry=0, state=None, sl
     what = "track_history"
     T, cap = _check_people(what, people, k)
     dev = people.device
-    _check_tensor(what, "prev", prev, dev, torch.int32, (T, cap))
-    if gap is not None:
-        _check_tensor(what, "gap", gap, dev, torch.int32, (T, cap))
-    Z = 0
-    if zones is not None:
-        _check_tensor(what, "zones", zones, dev)
-        if (zones.dtype != torch.float64 or zones.dim() != 2 or zones.shape[1] != 4
-                or not 1 <= zones.shape[0] <= MAX_TABLE):
-            raise ValueError(f"{what}: zones must be (n, 4) float64 with 1 <= n <= {MAX_TABLE}, got {zones.dtype} "
-                             f"{tuple(zones.shape)}")
-        Z = zones.shape[0]
-    if int(carry) != carry or not 0 <= carry <= T:
-        raise ValueError(f"{what}: carry must be an integer in 0 .. T = {T}, got {carry}")
-    carry = int(carry)
-    shapes = _history_shapes(T, cap, Z)
-    if state is None:
-        if carry:
-            raise ValueError(f"{what}: carried frames need their state")
-        state = tuple(torch.empty(shape, dtype=dtype, device=dev) for _, dtype, shape in shapes)
-    state = tuple(state)
-    if len(state) != len(shapes):
-        raise ValueError(f"{what}: state is (age, hits, path, origin"
-                         + (", stay) with zones" if Z else ") without zones"))
-    for t, (name, dtype, shape) in zip(state, shapes):
-        _check_tensor(what, name, t, dev, dtype, shape)
-    age, hits, path, origin = state[:4]
-    stay = state[4] if Z else None
-    dwell = torch.empty((T - carry, Z, 3), dtype=torch.int64, device=dev) if Z else None
+    _check_links(what, people, prev, gap)
+    Z = _check_device_table(what, "zones", zones, dev)
+    carry = _integer(what, "carry", carry, T, "T = ")
+    state = _take(what, "state", state, history_layout(T, cap, Z), dev, " with zones" if Z else " without zones",
+                  carry=carry)
+    # age, hits, path, origin, stay, dwell: without zones the state has no stay
+    out = state + ((torch.empty((T - carry, Z, 3), dtype=torch.int64, device=dev),) if Z else (None, None))
     if T > carry:  # an empty tensor has no address to pass
         nat.call("lidar_track_history_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
-                 nat.ptr(gap), T, cap, carry, nat.ptr(zones), Z, nat.ptr(age), nat.ptr(hits), nat.ptr(path),
-                 nat.ptr(origin), nat.ptr(stay), nat.ptr(dwell), nat.stream_ptr())
-    return age, hits, path, origin, stay, dwell
+                 nat.ptr(gap), T, cap, carry, nat.ptr(zones), Z, *(nat.ptr(t) for t in out), nat.stream_ptr())
+    return out
 
 
 class PeopleTracker:
@@ -306,18 +296,18 @@ class PeopleTracker:
     to max_gap missed frames, and (with a venue extent) the flow cells of everything pushed so far.
 
     push(people, k) takes a batch of any T >= 0 consecutive frames (cap is fixed by the first push).  The
-    tracker keeps the last min(max_gap + 1, frames seen) frames on the device — people, k and the five state
-    arrays — prepends them to the batch, and calls lidar_track_stream_f64 with them as the carry; with an
-    extent it then calls lidar_flow_cells_acc_f64(first = carry, accumulate = 1) into its own count / vsum.
-    Whatever the batch sizes, the outputs are those of one call over the whole stream, bit for bit.  Nothing
-    is synchronised.  ntracks () int64, matched () int64 (detections with a measured velocity), count (nx, ny)
-    int32 and vsum (nx, ny, 2) float64 are device tensors (count / vsum None without an extent); frames is the
-    number of frames seen.
+    tracker keeps the last min(max_gap + 1, frames seen) frames on the device in one window (layout(): people, k
+    and the five state arrays; held() returns it by name), extends it by the batch, and calls
+    lidar_track_stream_f64 with the held frames as the carry; with an extent it then calls
+    lidar_flow_cells_acc_f64(first = carry, accumulate = 1) into its own count / vsum.  Whatever the batch sizes,
+    the outputs are those of one call over the whole stream, bit for bit.  Nothing is synchronised.  ntracks ()
+    int64, matched () int64 (detections with a measured velocity), count (nx, ny) int32 and vsum (nx, ny, 2)
+    float64 are device tensors (count / vsum None without an extent); frames is the number of frames seen.
 
     gates (G, 4) and / or zones (Z, 4), array-likes as check_gates / check_zones take them, are validated here
     and uploaded once, at the first push; push then also calls lidar_track_events_f64(first = carry) and adds the
     new frames' counts into gate_total (G, 2) int64 (forward, backward) and zone_total (Z, 2) int64 (entries,
-    exits), device tensors (G or Z = 0 for an absent kind; occupancy is per frame and not accumulated).
+    exits), device tensors (the attributes G and Z: 0 for an absent kind; occupancy is per frame and not accumulated).
     last_events: track_events' five arrays for the frames of the last push.  However the stream is cut into
     pushes, the concatenated last_events and the totals are those of one call over the whole stream.  Without
     gates and zones the three stay None and push makes no further call.
@@ -333,7 +323,7 @@ class PeopleTracker:
     def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0, gates=None,
                  zones=None, history=False):
         self.dt, self.gate = _positive("PeopleTracker", "dt", dt), _positive("PeopleTracker", "gate", gate)
-        self.max_gap = _max_gap("PeopleTracker", max_gap)
+        self.max_gap = _integer("PeopleTracker", "max_gap", max_gap, MAX_GAP)
         if (x_range is None) != (y_range is None):
             raise ValueError("PeopleTracker: x_range and y_range go together")
         self.x_range, self.y_range, self.grid = x_range, y_range, None
@@ -344,14 +334,30 @@ class PeopleTracker:
         self.frames = 0
         self.cap = None
         self.ntracks = self.matched = self.count = self.vsum = None
-        self._carry = None  # (people, k, prev, gap, succ, velocity, track_id) of the last frames
         self._tables = (None if gates is None else check_gates(gates), None if zones is None else check_zones(zones))
-        self.events = any(t is not None for t in self._tables)
+        self.G, self.Z = (0 if t is None else t.shape[0] for t in self._tables)
+        self.events = self.G + self.Z > 0
         self.gate_total = self.zone_total = self.last_events = None
-        self._held_events = None  # track_events' arrays of the frames in _carry
         self.history = bool(history)
         self.last_history = self.dwell_total = None
-        self._held_history = None  # track_history's state (age, hits, path, origin[, stay]) of the frames in _carry
+        self._window = None  # name -> tensor: the last frames' arrays, layout()'s rows
+
+    def layout(self, T):
+        """(name, dtype, shape) of every array held, over T frames: people, k, STATE's five, track_events' arrays with
+        gates / zones (no mask of an absent kind), track_history's state arrays with history=True.  cap: 1 before
+        the first push."""
+        cap = self.cap or 1
+        rows = (("people", torch.float64, (T, cap, 2)), ("k", torch.int64, (T,))) + state_layout(T, cap)
+        if self.events:
+            rows += event_layout(T, cap, self.G, self.Z)
+        if self.history:
+            rows += history_layout(T, cap, self.Z)
+        return tuple(row for row in rows if row[2] is not None)
+
+    def held(self):
+        """name -> device tensor under layout()'s names: the last min(max_gap + 1, frames) frames as they stand now
+        (a later push may set succ in them).  Empty before the first push."""
+        return dict(self._window or {})
 
     def push(self, people, k):
         """-> (prev, gap, track_id, velocity) of the T new frames, device tensors."""
@@ -365,61 +371,47 @@ class PeopleTracker:
                 with nat.grid_alloc():
                     self.count = torch.zeros(self.grid[2:], dtype=torch.int32, device=dev)
                     self.vsum = torch.zeros(self.grid[2:] + (2,), dtype=torch.float64, device=dev)
-            self._carry = (people[:0], k[:0]) + tuple(torch.empty((0, cap) + tail, dtype=dtype, device=dev)
-                                                      for _, dtype, tail in STATE)
+            self._window = {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in self.layout(0)}
             if self.events:
                 self._tables = tuple(None if t is None else torch.from_numpy(t).to(dev) for t in self._tables)
-                G, Z = (0 if t is None else t.shape[0] for t in self._tables)
-                self.gate_total = torch.zeros((G, 2), dtype=torch.int64, device=dev)
-                self.zone_total = torch.zeros((Z, 2), dtype=torch.int64, device=dev)
-                self._held_events = tuple(None if shape is None else torch.empty(shape, dtype=dtype, device=dev)
-                                          for _, dtype, shape in _event_shapes(0, cap, G, Z))
-            if self.history:
-                Z = 0 if self._tables[1] is None else self._tables[1].shape[0]  # a zones table was uploaded above
-                self._held_history = tuple(torch.empty(shape, dtype=dtype, device=dev)
-                                           for _, dtype, shape in _history_shapes(0, cap, Z))
-                if Z:
-                    self.dwell_total = torch.zeros((Z, 3), dtype=torch.int64, device=dev)
+                self.gate_total = torch.zeros((self.G, 2), dtype=torch.int64, device=dev)
+                self.zone_total = torch.zeros((self.Z, 2), dtype=torch.int64, device=dev)
+            if self.history and self.Z:
+                self.dwell_total = torch.zeros((self.Z, 3), dtype=torch.int64, device=dev)
         if cap != self.cap or dev != self.ntracks.device:
             raise ValueError(f"PeopleTracker.push: cap and device are fixed by the first push ({self.cap}, "
                              f"{self.ntracks.device}), got {cap}, {dev}")
         if (self.frames + T) * cap >= 1 << 31:  # every row could be a new detection: the ids are int32
             raise ValueError(f"PeopleTracker.push: {self.frames + T} frames of {cap} rows could pass 2^31 track ids")
-        C = self._carry[0].shape[0]
-        if T == 0:
-            if self.events:
-                self.last_events = tuple(None if t is None else t[C:] for t in self._held_events)
-            if self.history:
-                Z = 0 if self._tables[1] is None else self._tables[1].shape[0]
-                self.last_history = tuple(t[C:] for t in self._held_history) + (
-                    (torch.empty((0, Z, 3), dtype=torch.int64, device=dev),) if Z else (None, None))
-            return tuple(self._carry[i][C:] for i in (2, 3, 6, 5))
-        people = torch.cat([self._carry[0], people])
-        k = torch.cat([self._carry[1], k])
-        state = tuple(torch.cat([c, torch.empty((T, cap) + tail, dtype=dtype, device=dev)])
-                      for c, (_, dtype, tail) in zip(self._carry[2:], STATE))
-        prev, gap, succ, velocity, track_id, _ = track_stream(people, k, self.dt, self.gate, self.max_gap, C, state,
-                                                              self.ntracks, self.slot)
-        self.matched += (prev[C:] >= 0).sum()
-        if self.grid is not None:
-            _flow_cells_acc(people, k, prev, velocity, C, 1, self.grid, self.grid_size, self.count, self.vsum,
-                            self.slot)
-        self.frames += T
-        keep = min(self.max_gap + 1, self.frames)
+        # the window extended by the batch: the C held frames, then the T new ones, which the calls below fill in place
+        C = self._window["k"].shape[0]
+        new = {"people": people, "k": k}
+        w = {name: torch.cat([self._window[name],
+                              new[name] if name in new else torch.empty(shape, dtype=dtype, device=dev)])
+             for name, dtype, shape in self.layout(T)}
+        people, k, prev, gap = w["people"], w["k"], w["prev"], w["gap"]
+        if T:  # an empty batch links nothing and moves no cell
+            track_stream(people, k, self.dt, self.gate, self.max_gap, C, tuple(w[name] for name, _, _ in STATE),
+                         self.ntracks, self.slot)
+            self.matched += (prev[C:] >= 0).sum()
+            if self.grid is not None:
+                _flow_cells_acc(people, k, prev, w["velocity"], C, 1, self.grid, self.grid_size, self.count, self.vsum,
+                                self.slot)
+        # track_events and track_history make no native call either when no frame follows the held ones
         if self.events:
-            self.last_events = track_events(people, k, prev, gap, *self._tables, first=C, slot=self.slot)
-            self.gate_total += self.last_events[0].sum(dim=0, dtype=torch.int64)
-            self.zone_total += self.last_events[1][:, :, 1:].sum(dim=0, dtype=torch.int64)
-            self._held_events = tuple(None if t is None else torch.cat([h, t])[C + T - keep:]
-                                      for h, t in zip(self._held_events, self.last_events))
+            out = tuple(w[name][C:] if name in w else None for name in EVENTS)
+            self.last_events = track_events(people, k, prev, gap, *self._tables, first=C, out=out, slot=self.slot)
+            self.gate_total += out[0].sum(dim=0, dtype=torch.int64)
+            self.zone_total += out[1][:, :, 1:].sum(dim=0, dtype=torch.int64)
         if self.history:
-            hstate = tuple(torch.cat([c, torch.empty((T,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev)])
-                           for c in self._held_history)
-            out = track_history(people, k, prev, gap, self._tables[1], C, hstate, self.slot)
+            state = tuple(w[name] for name, _, _ in history_layout(C + T, cap, self.Z))
+            out = track_history(people, k, prev, gap, self._tables[1], C, state, self.slot)
             self.last_history = tuple(None if t is None else t[C:] for t in out[:5]) + (out[5],)
             if out[5] is not None:
                 self.dwell_total[:, :2] += out[5][:, :, :2].sum(dim=0)
-                self.dwell_total[:, 2] = torch.maximum(self.dwell_total[:, 2], out[5][:, :, 2].amax(dim=0))
-            self._held_history = tuple(t[C + T - keep:] for t in hstate)
-        self._carry = tuple(t[C + T - keep:] for t in (people, k, prev, gap, succ, velocity, track_id))
-        return prev[C:], gap[C:], track_id[C:], velocity[C:]
+                # the largest of the total and the new frames: no reduction over an empty frame axis at T == 0
+                self.dwell_total[:, 2] = torch.cat([self.dwell_total[None, :, 2], out[5][:, :, 2]]).amax(dim=0)
+        self.frames += T
+        keep = min(self.max_gap + 1, self.frames)
+        self._window = {name: t[C + T - keep:] for name, t in w.items()}
+        return prev[C:], gap[C:], w["track_id"][C:], w["velocity"][C:]

@@ -14,13 +14,11 @@ from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: 
 from lidar_ai_recommendation_software_amd import pointnet2 as pn  # noqa: E402
 from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel  # noqa: E402
 
+from track_gpu_helpers import dev  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = ("prev", "track_id", "velocity", "ntracks")
-
-
-def dev(cuda, a):
-    return torch.from_numpy(np.array(a)).to(cuda)
 
 
 def run(cuda, people, k, dt, gate):

@@ -14,19 +14,9 @@ from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
 from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel  # noqa: E402
 
+from track_gpu_helpers import dev, pieces_of  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-
-def pieces_of(T):
-    """tests/test_gpu_track_stream.py's uneven pieces 1, 2, 0, 3, ... that add up to T."""
-    out, want = [], [1, 2, 0, 3, 1, 2]
-    while sum(out) < T:
-        out.append(min(want[len(out) % len(want)], T - sum(out)))
-    return out
-
-
-def dev(cuda, a):
-    return None if a is None else torch.from_numpy(np.array(a)).to(cuda)
 
 
 def same(got, want, what=""):

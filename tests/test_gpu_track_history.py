@@ -16,19 +16,9 @@ from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
 from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel  # noqa: E402
 
+from track_gpu_helpers import dev, pieces_of  # noqa: E402
+
 pytestmark = pytest.mark.gpu
-
-
-def pieces_of(T):
-    """tests/test_gpu_track_stream.py's uneven pieces 1, 2, 0, 3, ... that add up to T."""
-    out, want = [], [1, 2, 0, 3, 1, 2]
-    while sum(out) < T:
-        out.append(min(want[len(out) % len(want)], T - sum(out)))
-    return out
-
-
-def dev(cuda, a):
-    return None if a is None else torch.from_numpy(np.array(a)).to(cuda)
 
 
 def same(got, want, what="", frames=slice(None)):
@@ -172,7 +162,7 @@ def test_hand_cases_of_the_heir_rule_and_the_link_guard(cuda):
 
 # ------------------------------------------------------------------ carry
 def sentinels(cuda, T, cap, Z):
-    return tuple(torch.full(shape, 77, dtype=dtype, device=cuda) for _, dtype, shape in pt._history_shapes(T, cap, Z))
+    return tuple(torch.full(shape, 77, dtype=dtype, device=cuda) for _, dtype, shape in pt.history_layout(T, cap, Z))
 
 
 @pytest.mark.parametrize("max_gap", [0, 2])
@@ -263,6 +253,7 @@ def test_split_equals_whole_through_the_tracker(cuda, case, max_gap):
     tracker = pt.PeopleTracker(ref.DT, gate, max_gap, xr, yr, grid, gates=gates, zones=zones, history=True)
     bare = pt.PeopleTracker(ref.DT, gate, max_gap, xr, yr, grid, gates=gates, zones=zones)
     hist, lo = [], 0
+    seen = {name: [] for name in ("prev", "gap", "track_id", "velocity") + eref.NAMES + href.STATE}
     for n in pieces_of(T):
         a = tracker.push(pd[lo:lo + n], kd[lo:lo + n])
         b = bare.push(pd[lo:lo + n], kd[lo:lo + n])
@@ -271,12 +262,25 @@ def test_split_equals_whole_through_the_tracker(cuda, case, max_gap):
         assert len(tracker.last_history) == 6 and all(t.shape[0] == n for t in tracker.last_history)
         hist.append(tracker.last_history)
         lo += n
+        # the window: the last min(max_gap + 1, frames so far) frames of everything pushed, returned or left so far
+        for name, t in zip(seen, a + tracker.last_events + tracker.last_history[:5]):
+            seen[name].append(t.cpu().numpy())
+        so_far = {name: np.concatenate(parts) for name, parts in seen.items()}
+        so_far.update(people=people[:lo], k=k[:lo], succ=np.zeros((lo, people.shape[1]), dtype=np.uint8))
+        t, j = np.nonzero(so_far["prev"] >= 0)  # a linked row marks its source, so_far["gap"] frames back
+        so_far["succ"][t - so_far["gap"][t, j], so_far["prev"][t, j]] = 1
+        keep = min(max_gap + 1, lo)
+        held = tracker.held()
+        assert set(held) == set(so_far) and tracker.frames == lo
+        for name, t in held.items():
+            g, w = t.cpu().numpy(), so_far[name][lo - keep:]
+            assert g.shape[0] == keep and g.dtype == w.dtype and g.tobytes() == w.tobytes(), (lo, name)
     same(tuple(torch.cat([h[i] for h in hist]) for i in range(6)), want, "last_history")
     total = tracker.dwell_total.cpu().numpy()
     d = want["dwell"]
     assert total.dtype == np.int64 and total.shape == (3, 3)
     assert np.array_equal(total[:, :2], d[:, :, :2].sum(axis=0)) and np.array_equal(total[:, 2], d[:, :, 2].max(axis=0))
-    assert bare.last_history is None and bare.dwell_total is None and bare._held_history is None
+    assert bare.last_history is None and bare.dwell_total is None and not set(href.STATE) & set(bare.held())
     assert int(tracker.ntracks) == int(bare.ntracks) and int(tracker.matched) == int(bare.matched)
     assert torch.equal(tracker.count, bare.count) and tracker.vsum.cpu().numpy().tobytes() == bare.vsum.cpu().numpy().tobytes()
     assert torch.equal(tracker.gate_total, bare.gate_total) and torch.equal(tracker.zone_total, bare.zone_total)

@@ -12,13 +12,11 @@ from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
 from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel  # noqa: E402
 
+from track_gpu_helpers import dev, pieces_of  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DTYPES = {"prev": np.int32, "gap": np.int32, "succ": np.uint8, "velocity": np.float64, "track_id": np.int32}
-
-
-def dev(cuda, a):
-    return torch.from_numpy(np.array(a)).to(cuda)
 
 
 def run(cuda, people, k, dt, gate, max_gap):
@@ -61,14 +59,6 @@ def test_max_gap_0_equals_track_people(cuda, case):
         assert int(ssucc.sum()) == int((prev >= 0).sum())
 
 
-def pieces_of(T):
-    """Uneven pieces 1, 2, 0, 3, ... that add up to T: the first is shorter than max_gap + 1 for max_gap >= 1."""
-    out, want = [], [1, 2, 0, 3, 1, 2]
-    while sum(out) < T:
-        out.append(min(want[len(out) % len(want)], T - sum(out)))
-    return out
-
-
 @pytest.mark.parametrize("case", sref.GAPPY, ids=str)
 @pytest.mark.parametrize("max_gap", [0, 1, 2])
 def test_split_equals_whole_through_the_tracker(cuda, case, max_gap):
@@ -101,7 +91,7 @@ def test_split_equals_whole_through_the_tracker(cuda, case, max_gap):
     assert tracker.vsum.cpu().numpy().tobytes() == wv.tobytes()
     # the frames the tracker holds: the whole's last min(max_gap + 1, T), succ included
     keep = min(max_gap + 1, T)
-    held = dict(zip(sref.STATE, (t.cpu().numpy() for t in tracker._carry[2:])))
+    held = {name: t.cpu().numpy() for name, t in tracker.held().items()}
     for name in sref.STATE:
         assert held[name].tobytes() == want[name][T - keep:].tobytes(), name
 
@@ -376,6 +366,32 @@ def test_tracker_and_wrapper_edges(cuda):
     assert int(tracker.ntracks) == int(k[0]) and int(tracker.count.sum()) == 0
     with pytest.raises(ValueError, match="cap"):
         tracker.push(pd[:1, :cap - 1].contiguous(), kd[:1])
+    # empty pushes through a tracker with a gate, a zone and history, the first of them before any frame: every
+    # output has its dtype and trailing shape and no frame, the totals stay what they were
+    full = pt.PeopleTracker(ref.DT, 0.5, 1, (0.0, 4.0), (0.0, 4.0), gates=[(2.0, 4.0, 2.0, 0.0)],
+                            zones=[(0.0, 2.0, 0.0, 4.0)], history=True)
+    p5 = np.full((3, 5, 2), np.nan)
+    p5[:, :2, 0] = [[1.5, 3.0], [1.9, 3.0], [2.25, 3.0]]  # row 0 walks east through the gate and out of the zone
+    p5[:, :2, 1] = 1.0
+    p5d, k5d = dev(cuda, p5), dev(cuda, np.array([2, 2, 2]))
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    totals = None
+    for lo, hi, frames in ((0, 0, 0), (0, 3, 3), (3, 3, 3)):
+        n = hi - lo
+        out = full.push(p5d[lo:hi], k5d[lo:hi])
+        assert [(t.dtype, tuple(t.shape)) for t in out] == [(i32, (n, 5)), (i32, (n, 5)), (i32, (n, 5)), (f64, (n, 5, 2))]
+        assert [(t.dtype, tuple(t.shape)) for t in full.last_events] == [
+            (i32, (n, 1, 2)), (i32, (n, 1, 3)), (i64, (n, 5)), (i64, (n, 5)), (i64, (n, 5))]
+        assert [(t.dtype, tuple(t.shape)) for t in full.last_history] == [
+            (i32, (n, 5)), (i32, (n, 5)), (f64, (n, 5)), (f64, (n, 5, 2)), (i32, (n, 5, 1)), (i64, (n, 1, 3))]
+        assert full.frames == frames
+        now = [t.cpu().numpy().copy() for t in (full.ntracks, full.matched, full.count, full.vsum, full.gate_total,
+                                                full.zone_total, full.dwell_total)]
+        if n == 0:
+            assert all(np.array_equal(a, b) if totals else not a.any() for a, b in zip(now, totals or now))
+        totals = now
+    assert int(full.ntracks) == 2 and full.gate_total.tolist() == [[1, 0]] and full.zone_total.tolist() == [[0, 1]]
+    assert full.dwell_total.tolist() == [[1, 1, 1]] and int(full.matched) == 4
     # the id bound is the host's: frames * cap, no read-back
     big = pt.PeopleTracker(ref.DT, 0.25)
     big.push(pd[:1], kd[:1])

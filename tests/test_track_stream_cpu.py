@@ -156,9 +156,60 @@ def test_entry_points_reject_bad_arguments_before_any_launch():
     assert lib.lidar_flow_cells_acc_f64(p, p, p, p, p, 0, cap, 0, 1, 0.0, 0.0, 1.0, 4, 4, p, p, None) == 0
 
 
-def test_python_validation_without_a_gpu():
+def host_tensors(monkeypatch, T=3, cap=4):
+    """Host tensors stand in for device tensors: people_tracking's tensor check keeps its dtype and shape test and
+    its message and drops the device, so the wrappers' later checks are reached without a GPU (each of them raises
+    before the native call).  -> (people (T, cap, 2), k (T,), prev (T, cap), velocity (T, cap, 2), table (1, 4))."""
+    torch = pytest.importorskip("torch")
+    from lidar_ai_recommendation_software_amd import people_tracking as pt
+
+    def on_host(what, name, t, dev=None, dtype=None, shape=None):
+        assert isinstance(t, torch.Tensor) and t.is_contiguous()
+        if dtype is not None and (t.dtype != dtype or tuple(t.shape) != shape):
+            raise ValueError(f"{what}: {name} must be {shape} {dtype}, got {t.dtype} {tuple(t.shape)}")
+
+    monkeypatch.setattr(pt, "_check_tensor", on_host)
+    return (torch.zeros((T, cap, 2), dtype=torch.float64), torch.zeros(T, dtype=torch.int64),
+            torch.zeros((T, cap), dtype=torch.int32), torch.zeros((T, cap, 2), dtype=torch.float64),
+            torch.zeros((1, 4), dtype=torch.float64))
+
+
+def test_python_validation_without_a_gpu(monkeypatch):
     from lidar_ai_recommendation_software_amd import people_tracking as pt
     from lidar_ai_recommendation_software_amd.crowd_flow_model import CrowdFlowModel
+    # every wrapper's first complaint carries its own name
+    ph, kh, lh = np.zeros((1, 4, 2)), np.zeros(1, dtype=np.int64), np.zeros((1, 4), dtype=np.int32)
+    for name, call in (("flow_cells", lambda: pt.flow_cells(ph, kh, lh, ph, (0.0, 1.0), (0.0, 1.0))),
+                       ("track_stream", lambda: pt.track_stream(ph, kh, 0.1, 0.3)),
+                       ("track_events", lambda: pt.track_events(ph, kh, lh, zones=ph[0])),
+                       ("track_history", lambda: pt.track_history(ph, kh, lh))):
+        with pytest.raises(ValueError, match=f"^{name}: people must be a contiguous CUDA tensor"):
+            call()
+    for bad in (-1, 8, 1.5):
+        with pytest.raises(ValueError, match="^PeopleTracker: max_gap must be an integer in 0 .. 7, got"):
+            pt.PeopleTracker(0.1, 0.3, max_gap=bad)
+    with monkeypatch.context() as m:
+        people, k, prev, velocity, table = host_tensors(m)
+        # the integer check through the other callers, each under its entry point's name, T = 3 frames
+        for bad in (-1, 8, 1.5):
+            with pytest.raises(ValueError, match="^track_stream: max_gap must be an integer in 0 .. 7, got"):
+                pt.track_stream(people, k, 0.1, 0.3, bad)
+        for bad in (-1, 4, 1.5):
+            with pytest.raises(ValueError, match=r"^track_stream: carry must be an integer in 0 .. min\(max_gap \+ 1, T\) = 3, got"):
+                pt.track_stream(people, k, 0.1, 0.3, 7, carry=bad)
+            with pytest.raises(ValueError, match="^track_events: first must be an integer in 0 .. T = 3, got"):
+                pt.track_events(people, k, prev, zones=table, first=bad)
+            with pytest.raises(ValueError, match="^track_history: carry must be an integer in 0 .. T = 3, got"):
+                pt.track_history(people, k, prev, carry=bad)
+        with pytest.raises(ValueError, match=r"^track_stream: carry must be an integer in 0 .. min\(max_gap \+ 1, T\) = 1, got 2"):
+            pt.track_stream(people, k, 0.1, 0.3, 0, carry=2)
+        # flow_cells: the links, the velocity and the grid size, before the grid is built
+        with pytest.raises(ValueError, match="^flow_cells: prev must be"):
+            pt.flow_cells(people, k, prev[:, :3].contiguous(), velocity, (0.0, 1.0), (0.0, 1.0))
+        with pytest.raises(ValueError, match="^flow_cells: velocity must be"):
+            pt.flow_cells(people, k, prev, velocity.float(), (0.0, 1.0), (0.0, 1.0))
+        with pytest.raises(ValueError, match="^flow_cells: grid_size must be positive and finite"):
+            pt.flow_cells(people, k, prev, velocity, (0.0, 1.0), (0.0, 1.0), grid_size=0.0)
     for bad in (-1, 8, 1.5):
         with pytest.raises(ValueError, match="max_gap"):
             pt.PeopleTracker(0.1, 0.3, max_gap=bad)

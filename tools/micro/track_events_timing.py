@@ -1,5 +1,5 @@
 """Gate and zone event timings on the GPU: 32 frames of 78, 1 024 and 4 096 walkers each
-(track_stream_timing.py's walkers, every walker left out of a frame with probability 0.1), max_gap = 1, through
+(track_common.py's walkers, every walker left out of a frame with probability 0.1), max_gap = 1, through
   * people_tracking.track_stream + flow_cells alone (what the events follow; the same figure on the commit before
     this operator and on this one shows whether tracking changed: `tracking` as an argument measures only this, and
     needs nothing this operator added),
@@ -22,6 +22,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
+from track_common import DT, timed, walkers  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 5
 small = "small" in sys.argv[1:]
@@ -29,47 +30,8 @@ tracking_only = "tracking" in sys.argv[1:]
 if not torch.cuda.is_available():
     sys.exit("track_events_timing.py measures on the GPU: no device visible")
 dev = torch.device("cuda:0")
-DT, MAX_SPEED, MISS, MAX_GAP = 0.1, 3.0, 0.1, 1
+MAX_SPEED, MISS, MAX_GAP = 3.0, 0.1, 1
 GATE = MAX_SPEED * DT
-
-
-def timed(fn, reps=reps, warm=3, windows=5):
-    """ms per call: (median, fastest, slowest) over `windows` windows of `reps` calls."""
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1) / reps)
-    ms.sort()
-    return [round(v, 4) for v in (ms[len(ms) // 2], ms[0], ms[-1])]
-
-
-def walkers(T, n, seed):
-    """(people (T, n, 2), k (T,), side): track_stream_timing.py's walkers (a square of side 0.75 sqrt(n) m, up to
-    1.5 m/s, reflected at the walls), each left out of a frame with probability MISS; the rows permuted per frame."""
-    rng = np.random.default_rng(seed)
-    side = 0.75 * np.sqrt(n)
-    pos = rng.uniform(0, side, (n, 2))
-    vel = rng.uniform(-1.5, 1.5, (n, 2)) / np.sqrt(2)
-    out = np.full((T, n, 2), np.nan)
-    k = np.empty(T, dtype=np.int64)
-    for t in range(T):
-        seen = np.flatnonzero(rng.random(n) >= MISS)
-        seen = seen[rng.permutation(len(seen))]
-        k[t] = len(seen)
-        out[t, :len(seen)] = pos[seen]
-        pos = pos + (vel + rng.normal(0, 0.1, (n, 2))) * DT
-        hit = (pos < 0) | (pos > side)
-        vel = np.where(hit, -vel, vel)
-        pos = np.clip(pos, 0, side)
-    return out, k, side
 
 
 def tables(n, side, seed):
@@ -124,7 +86,7 @@ def composed(people, k, prev, gap, gates, zones):
 T = 4 if small else 32
 rows_out = []
 for n in ((20, 300) if small else (78, 1024, 4096)):
-    ph, kh, side = walkers(T, n, 40 + n)
+    ph, kh, side = walkers(T, n, 40 + n, MISS)
     people, k = torch.from_numpy(ph).to(dev), torch.from_numpy(kh).to(dev)
     xr = yr = (0.0, float(side))
 
@@ -134,7 +96,7 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         return prev, gap
 
     row = {"frames": T, "people": n, "detections": int(kh.sum()), "max_gap": MAX_GAP,
-           "track_stream_and_cells_ms": timed(tracking)}
+           "track_stream_and_cells_ms": timed(tracking, reps)}
     prev, gap = tracking()
     for size in (() if tracking_only else (8, 64)):
         gates, zones = (torch.from_numpy(a).to(dev) for a in tables(size, side, 7 + size))
@@ -150,9 +112,10 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         nat.profile(nat.handle(dev.index), False)
         row[f"tables_{size}"] = {
             "crossings": int(out[0].sum()), "entries": int(out[1][:, :, 1].sum()), "composition_equals_kernel": same,
-            "track_events_ms": timed(lambda: pt.track_events(people, k, prev, gap, gates, zones)),
-            "track_events_out_ms": timed(lambda: pt.track_events(people, k, prev, gap, gates, zones, out=out)),
-            "torch_composition_ms": timed(lambda: composed(people, k, prev, gap, gates, zones)), "spans_ms": spans}
+            "track_events_ms": timed(lambda: pt.track_events(people, k, prev, gap, gates, zones), reps),
+            "track_events_out_ms": timed(lambda: pt.track_events(people, k, prev, gap, gates, zones, out=out), reps),
+            "torch_composition_ms": timed(lambda: composed(people, k, prev, gap, gates, zones), reps),
+            "spans_ms": spans}
     rows_out.append(row)
     print(json.dumps(row), flush=True)
 

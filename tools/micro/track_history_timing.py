@@ -1,5 +1,5 @@
 """Track history timings on the GPU: 32 frames of 78, 1 024 and 4 096 walkers each
-(track_events_timing.py's walkers, every walker left out of a frame with probability 0.1), max_gap = 1, through
+(track_common.py's walkers, every walker left out of a frame with probability 0.1), max_gap = 1, through
   * people_tracking.track_stream + flow_cells alone (the tracking the history follows), in the same visit,
   * people_tracking.track_history on their prev / gap with Z = 0, 8 and 64 zones, outputs allocated and state= given,
   * a device-side torch composition of the same recurrence, frame by frame: a gather of the sources' state per frame
@@ -21,53 +21,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, REPO)
 from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
+from track_common import DT, timed, walkers  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 20
 small = "small" in sys.argv[1:]
 if not torch.cuda.is_available():
     sys.exit("track_history_timing.py measures on the GPU: no device visible")
 dev = torch.device("cuda:0")
-DT, MAX_SPEED, MISS, MAX_GAP = 0.1, 3.0, 0.1, 1
+MAX_SPEED, MISS, MAX_GAP = 3.0, 0.1, 1
 GATE = MAX_SPEED * DT
-
-
-def timed(fn, reps=reps, warm=3, windows=5):
-    """ms per call: (median, fastest, slowest) over `windows` windows of `reps` calls."""
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1) / reps)
-    ms.sort()
-    return [round(v, 4) for v in (ms[len(ms) // 2], ms[0], ms[-1])]
-
-
-def walkers(T, n, seed):
-    """(people (T, n, 2), k (T,), side): track_events_timing.py's walkers (a square of side 0.75 sqrt(n) m, up to
-    1.5 m/s, reflected at the walls), each left out of a frame with probability MISS; the rows permuted per frame."""
-    rng = np.random.default_rng(seed)
-    side = 0.75 * np.sqrt(n)
-    pos = rng.uniform(0, side, (n, 2))
-    vel = rng.uniform(-1.5, 1.5, (n, 2)) / np.sqrt(2)
-    out = np.full((T, n, 2), np.nan)
-    k = np.empty(T, dtype=np.int64)
-    for t in range(T):
-        seen = np.flatnonzero(rng.random(n) >= MISS)
-        seen = seen[rng.permutation(len(seen))]
-        k[t] = len(seen)
-        out[t, :len(seen)] = pos[seen]
-        pos = pos + (vel + rng.normal(0, 0.1, (n, 2))) * DT
-        hit = (pos < 0) | (pos > side)
-        vel = np.where(hit, -vel, vel)
-        pos = np.clip(pos, 0, side)
-    return out, k, side
 
 
 def zone_table(n, side, seed):
@@ -137,7 +99,7 @@ def check(out, ref, what):
 T = 4 if small else 32
 rows_out = []
 for n in ((20, 300) if small else (78, 1024, 4096)):
-    ph, kh, side = walkers(T, n, 40 + n)
+    ph, kh, side = walkers(T, n, 40 + n, MISS)
     people, k = torch.from_numpy(ph).to(dev), torch.from_numpy(kh).to(dev)
     xr = yr = (0.0, float(side))
 
@@ -147,7 +109,7 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         return prev, gap
 
     row = {"frames": T, "people": n, "detections": int(kh.sum()), "max_gap": MAX_GAP,
-           "track_stream_and_cells_ms": timed(tracking)}
+           "track_stream_and_cells_ms": timed(tracking, reps)}
     prev, gap = tracking()
     for Z in (0, 8, 64):
         zones = torch.from_numpy(zone_table(Z, side, 7 + Z)).to(dev) if Z else None
@@ -158,14 +120,14 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         pt.track_history(people, k, prev, gap, zones, state=state)
         spans = {name: round(ms, 4) for name, ms in nat.profile_read(nat.handle(dev.index))}
         nat.profile(nat.handle(dev.index), False)
-        ms = timed(lambda: pt.track_history(people, k, prev, gap, zones))
+        ms = timed(lambda: pt.track_history(people, k, prev, gap, zones), reps)
         row[f"zones_{Z}"] = {
             "links": int((prev >= 0).sum()), "walk_starts": int((prev < 0).sum() - (T * n - int(kh.sum()))),
             "completed_stays": int(out[5][:, :, 0].sum()) if Z else 0, "composition_equals_kernel": True,
             "track_history_ms": ms,
-            "track_history_state_ms": timed(lambda: pt.track_history(people, k, prev, gap, zones, state=state)),
+            "track_history_state_ms": timed(lambda: pt.track_history(people, k, prev, gap, zones, state=state), reps),
             "share_of_tracking": round(ms[0] / row["track_stream_and_cells_ms"][0], 3),
-            "torch_composition_ms": timed(lambda: composed(people, k, prev, gap, zones)),
+            "torch_composition_ms": timed(lambda: composed(people, k, prev, gap, zones), reps),
             "spans_ms": spans}
     rows_out.append(row)
     print(json.dumps(row), flush=True)

@@ -15,66 +15,26 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, REPO)
 from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
 from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
+from track_common import DT, timed, walkers  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 5
 small = "small" in sys.argv[1:]
 if not torch.cuda.is_available():
     sys.exit("track_stream_timing.py measures on the GPU: no device visible")
 dev = torch.device("cuda:0")
-DT, MAX_SPEED, MISS = 0.1, 3.0, 0.1
+MAX_SPEED, MISS = 3.0, 0.1
 GATE = MAX_SPEED * DT
-
-
-def timed(fn, reps=reps, warm=3, windows=5):
-    """ms per call: (median, fastest, slowest) over `windows` windows of `reps` calls."""
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1) / reps)
-    ms.sort()
-    return [round(v, 4) for v in (ms[len(ms) // 2], ms[0], ms[-1])]
-
-
-def walkers(T, n, seed):
-    """(people (T, n, 2), k (T,), side): track_timing.py's walkers (a square of side 0.75 sqrt(n) m, up to 1.5 m/s,
-    reflected at the walls), each left out of a frame with probability MISS; the rows permuted per frame."""
-    rng = np.random.default_rng(seed)
-    side = 0.75 * np.sqrt(n)
-    pos = rng.uniform(0, side, (n, 2))
-    vel = rng.uniform(-1.5, 1.5, (n, 2)) / np.sqrt(2)
-    out = np.full((T, n, 2), np.nan)
-    k = np.empty(T, dtype=np.int64)
-    for t in range(T):
-        seen = np.flatnonzero(rng.random(n) >= MISS)
-        seen = seen[rng.permutation(len(seen))]
-        k[t] = len(seen)
-        out[t, :len(seen)] = pos[seen]
-        pos = pos + (vel + rng.normal(0, 0.1, (n, 2))) * DT
-        hit = (pos < 0) | (pos > side)
-        vel = np.where(hit, -vel, vel)
-        pos = np.clip(pos, 0, side)
-    return out, k, side
-
 
 T, PIECE = (4, 2) if small else (32, 8)
 rows_out = []
 for n in ((20, 300) if small else (78, 1024, 4096)):
-    ph, kh, side = walkers(T, n, 40 + n)
+    ph, kh, side = walkers(T, n, 40 + n, MISS)
     people, k = torch.from_numpy(ph).to(dev), torch.from_numpy(kh).to(dev)
     xr = yr = (0.0, float(side))
 
@@ -94,7 +54,7 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         return tracker
 
     row = {"frames": T, "people": n, "detections": int(kh.sum()), "piece": PIECE,
-           "track_people_and_cells_ms": timed(pairwise)}
+           "track_people_and_cells_ms": timed(pairwise, reps)}
     for max_gap in (0, 1, 2):
         prev, gap, nt, count, vsum = one_call(max_gap)
         tracker = pushed(max_gap)
@@ -108,7 +68,7 @@ for n in ((20, 300) if small else (78, 1024, 4096)):
         row[f"max_gap_{max_gap}"] = {
             "tracks": int(nt), "matched_share": float((prev[1:] >= 0).sum()) / max(1, int(kh[1:].sum())),
             "stitched_share_of_matched": float((gap >= 2).sum()) / max(1, int((prev >= 0).sum())),
-            "one_call_ms": timed(lambda: one_call(max_gap)), "pushed_ms": timed(lambda: pushed(max_gap)),
+            "one_call_ms": timed(lambda: one_call(max_gap), reps), "pushed_ms": timed(lambda: pushed(max_gap), reps),
             "pushed_equals_one_call": same, "spans_ms": spans}
     rows_out.append(row)
     print(json.dumps(row), flush=True)
