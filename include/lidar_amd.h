@@ -356,7 +356,8 @@ enum {
     LIDAR_S_SCALER_MEAN = 22,   /* 22..24: StandardScaler mean */
     LIDAR_S_SCALER_SCALE = 25,  /* 25..27: StandardScaler scale */
     LIDAR_S_SCALED_BBOX = 28,   /* 28..33: lo (3), hi (3) of the scaled non-ground points */
-    LIDAR_S_N_CLUSTERS = 39,
+    LIDAR_S_N_CLUSTERS = 39,    /* max label + 1 of the frame: DBSCAN's cluster count; 1 when DBSCAN is skipped (1..10
+                                   non-ground points, all label 0); 0 without non-ground points or for a failed frame */
     LIDAR_S_PLANE_KIND = 40,    /* 0 lstsq, 1 min-z fallback, 2 rank-deficient ground */
     LIDAR_SCALARS = 64,
     LIDAR_STATUS_OK = 0,

@@ -138,6 +138,93 @@ LIDAR_EXPORT int lidar_debug_fill_workspace(lidar_handle *h, uint64_t bytes, uin
     return LIDAR_OK;
 }
 
+namespace {
+// the poison of word i: 1 + a hash of (i, seed) modulo bound, high half zero
+__device__ __forceinline__ unsigned long long poison_word(uint64_t i, unsigned long long seed, unsigned long long bound)
+{
+    unsigned long long z = (i + 1) * 0x9E3779B97F4A7C15ull + seed * 0xD1B54A32D192ED03ull;
+    z ^= z >> 29;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 32;
+    return 1ull + z % bound;
+}
+
+__global__ void poison_workspace_kernel(unsigned long long *w, uint64_t words, unsigned long long seed,
+                                        unsigned long long bound)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x)
+        w[i] = poison_word(i, seed, bound);
+}
+
+__global__ void count_poison_kernel(const unsigned long long *w, uint64_t words, unsigned long long bound,
+                                    unsigned long long *count)
+{
+    unsigned long long mine = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long v = w[i];
+        mine += (v >= 1 && v <= bound) ? 1 : 0;  // bound < 2^32: the high half is zero
+    }
+    if (mine) atomicAdd(count, mine);
+}
+}  // namespace
+
+// Testing aid: grows the workspace to `bytes` and fills the whole block, on `stream`, so that every aligned
+// 64-bit word holds a value in [1, bound] (a function of word index and seed; 1 <= bound < 2^32, so the
+// high half is zero).  As int64 or the even int32 slots the poison is a small non-zero number, as double
+// or float a positive denormal, as uint8 flags small and non-zero: an operator that wrongly consumes a
+// stale word as a count or an index gets a value within `bound`, so the bug shows as a wrong result
+// (tests/test_gpu_workspace_leftovers.py).
+LIDAR_EXPORT int lidar_debug_poison_workspace(lidar_handle *h, uint64_t bytes, uint64_t bound, uint64_t seed,
+                                              void *stream)
+{
+    REQUIRE(h != nullptr, "lidar_debug_poison_workspace: null handle");
+    REQUIRE(bound >= 1 && bound <= 0xffffffffull, "lidar_debug_poison_workspace: bound outside [1, 2^32)");
+    ON_DEVICE(h->device);
+    if (!lidar::workspace(h, bytes)) return LIDAR_ENOMEM;
+    const uint64_t words = h->ws_bytes / 8;
+    if (words == 0) return LIDAR_OK;
+    hipLaunchKernelGGL(poison_workspace_kernel, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<unsigned long long *>(h->ws), words, (unsigned long long)seed,
+                       (unsigned long long)bound);
+    LAUNCH_CHECK();
+    return LIDAR_OK;
+}
+
+// Testing aid: the live block's address and size, and how many of its 64-bit words still match the poison
+// predicate (high half zero, low half in [1, bound]), counted on `stream` and read back after
+// synchronising it.  Never grows the block.
+LIDAR_EXPORT int lidar_debug_workspace_info(lidar_handle *h, void **ptr, uint64_t *bytes, uint64_t *poisoned_words,
+                                            uint64_t bound, void *stream)
+{
+    REQUIRE(h && ptr && bytes && poisoned_words, "lidar_debug_workspace_info: null pointer");
+    REQUIRE(bound >= 1 && bound <= 0xffffffffull, "lidar_debug_workspace_info: bound outside [1, 2^32)");
+    ON_DEVICE(h->device);
+    *ptr = h->ws;
+    *bytes = h->ws_bytes;
+    *poisoned_words = 0;
+    const uint64_t words = h->ws_bytes / 8;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (words == 0) {
+        HIP_TRY(hipStreamSynchronize(s));
+        return LIDAR_OK;
+    }
+    unsigned long long *count = nullptr;
+    HIP_TRY(hipMalloc(&count, sizeof(*count)));
+    unsigned long long got = 0;
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(*count), s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(count_poison_kernel, dim3(1024), dim3(256), 0, s,
+                           static_cast<const unsigned long long *>(h->ws), words, (unsigned long long)bound, count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&got, count, sizeof(got), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(count);
+    if (e != hipSuccess) return lidar::fail(LIDAR_EHIP, std::string("lidar_debug_workspace_info: ") + hipGetErrorString(e));
+    *poisoned_words = got;
+    return LIDAR_OK;
+}
+
 // Testing aid: sets the handle's call epoch (the next voxel call takes epoch + 1; 0xffffffff: it wraps).
 LIDAR_EXPORT int lidar_debug_set_epoch(lidar_handle *h, uint32_t epoch)
 {

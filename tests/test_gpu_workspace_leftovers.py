@@ -1,0 +1,1161 @@
+"""No operator may trust what an earlier call left in the handle's workspace.
+
+Every operator that takes scratch memory from ``lidar::workspace(h, bytes)`` runs here on the diagnostic library
+(``diag_lib.diag_library``: the package's own wrappers and entry points, on one handle) after the block was
+dirtied in four ways:
+
+* **poison** — ``lidar_debug_poison_workspace``: every 64-bit word of the block a value in [1, bound], bound the
+  call's smallest extent, two seeds.  As an integer a stale word is a small count or index, as a float a positive
+  denormal, as a byte flag non-zero: a kernel that consumes one gives a wrong result, not a wild access.
+* **same layout** — the same operator, shapes and arguments on other data.
+* **shrink** — the same operator at larger extents (the same carve-up where padding allows it), so that the earlier
+  call's real data lies just past this call's end.
+* **other operator** — a call of another family whose every extent is at most this call's.
+
+After every run: the block's address and size are what they were before the call (``POISON_BYTES``, 64 MiB, is
+requested by the first poison of every test and is far above the largest need in this file, 6 MiB for the
+298 000-point FPS frame: no call ever grows the block, which would hand it a fresh one); in the poison regime
+fewer words match the poison predicate after the call than before it (the poison lay where the operator works);
+the outputs equal the operator's existing oracle, and are bit-identical to the same call on a newly created
+handle; output buffers are pre-filled with a sentinel, which everything past the operator's extent (and what its
+specification calls untouched) still holds.  Caller-side buffers are allocated with slack up to the largest
+dirtying call's extents and the call gets a prefix view, inputs padded with 0.5 and outputs with the sentinel, so
+a stale index a hypothetical bug followed would stay inside memory the test owns.
+
+The carve-ups, one sentence per sub-buffer: who writes it before whom.
+
+FPS (fps.hip, per frame b at ``ws + b * stride``, stride = align64(5 * npad) floats)
+  * ``p`` float4[npad]: fps_prologue scatters all n points into [0, n) by Morton cell and writes the sentinel rows
+    [n, npad) before its closing barrier; the bbox pass and the step loop read after that barrier.
+  * ``d`` float[npad]: fps_prologue writes inf over [0, n) and -1 over [n, npad) at the same place; the step loop
+    reads and updates it afterwards.  The stride's alignment gap is never touched.
+Ball query through the handle (ball_query.hip, per frame ``BqGrid | tab[kTab + 64] | sorted float4[n]``)
+  * ``BqGrid``: thread 0 of bq_bin_kernel writes every field (pad included); bq_grid_kernel is the next launch.
+  * ``tab``: bq_bin_kernel writes slots [0, kTab] from its LDS scan; the query reads slots <= kTab only; the 63
+    words of padding are neither written nor read.
+  * ``sorted``: bq_bin_kernel writes all n rows (every point lands in one slot); the query reads rows below tab[kTab] = n.
+Voxel, single-frame entry (voxel.hip)
+  * the batched path's carve-up (keys, bucket tables, in-launch hand-offs through the handle's tag block: its own
+    test, test_voxel_ignores_workspace_leftovers) for one frame, then
+  * ``dn``, one int32 256 bytes before the end of the request: the batched path writes nvox[0] there (a failure
+    code included) before the copy to the pinned host word on the same stream.
+DBSCAN and radius count (dbscan.hip carve_dbscan, run_dbscan_on)
+  * ``P`` double[20]: copied whole from the pinned host block (zeroed, then n, eps, active) before every launch;
+    dbscan_bbox_kernel writes lo / hi, dbscan_setup_kernel the grid slots, dbscan_labels_kernel the cluster count.
+  * ``cid``, ``parent``: dbscan_cells_kernel writes [0, n) before the scatter, the unions and the labels read them.
+  * ``cellcnt``: fill_u32_kernel zeroes ncell + 1 counters before dbscan_cells_kernel adds to them.
+  * ``cellstart``: the exclusive scan of cellcnt writes ncell + 1 entries before the copy and every neighbour walk.
+  * ``fill``: copy of cellstart before the scatter's atomics; refilled with kNoCore before dbscan_count_kernel's atomicMin.
+  * ``order``, ``sxyz``: dbscan_scatter_kernel writes [0, n) (a permutation) before dbscan_count_kernel reads them.
+  * ``cnt``, ``core``: dbscan_count_kernel writes [0, n) before the unions, roots and labels (and the counts copy) read them.
+  * ``flag``: dbscan_roots_kernel writes [0, n) before the rank scan reads n entries.
+  * ``rank``: the scan writes n + 1 entries before dbscan_labels_kernel reads rank[parent] and rank[n].
+  * ``partial``: scan_partial_kernel writes one word per block before scan_top_kernel / scan_final_kernel read them.
+Preprocess chain (preprocess.hip run_preprocess, one slice of ``wss`` bytes per frame)
+  * ``sc`` double[3n], ``ng_pos`` int32[n]: preprocess_kernel writes the nng scaled non-ground rows before DBSCAN
+    (as its ``x``) and scatter_labels2_kernel read [0, nng).
+  * ``ng_lab`` int64[n]: dbscan_labels_kernel writes [0, nng) of an active frame; scatter_labels2_kernel reads it
+    only when nng > 10, which is when the frame is active.
+  * the DBSCAN sub-buffers as above, with ``P`` written by dbscan_params_from_preprocess from the frame's scalars.
+    That kernel left P[P_NCLUST] to dbscan_labels_kernel, which skips an inactive frame (failed, or <= 10
+    non-ground points): nclust_kernel then copied a stale word into the public LIDAR_S_N_CLUSTERS slot.  Found by
+    this reading, fixed there (dbscan_params_from_preprocess now writes the slot), pinned by the scalars checks below.
+People / density grid / density batch / histogram2d (density_grid.hip)
+  * lidar_people_f64 ``kd`` int64: hipMemsetAsync to 0 before max_label_kernel's atomicMax and people_kernel's read.
+  * lidar_density_grid_f64 ``xe``, ``ye``, ``count``: density_body writes all of them (count zeroed) before its first
+    barrier, bins after it; ``pos``: thread 0 writes pos[0 .. np) before np_sum reads that range; ``k``: copied from
+    the pinned host word before the launch.
+  * lidar_density_batch_f64 ``scratch``: the same four per frame at the job's offset, by the same body.
+  * lidar_histogram2d_f64 ``cnt``: hipMemsetAsync over bx * by words before hist2d_kernel adds and the finish reads.
+Class people (class_people.hip, per-frame slices then frame-major rows)
+  * ``flag`` (the slice's DbscanWs::flag), ``part``: flag_kernel writes [0, n) and one record per workgroup, and
+    P[P_NALL] = n, before the rank scan and params_kernel read them.
+  * ``rank``: the scan writes n + 1 entries before scatter_kernel and params_kernel (rank[n] = nsel) read them.
+  * ``pos``: scatter_kernel writes [0, n) before instance_kernel reads it; ``xs``, ``xall``: it writes the nsel
+    selected rows before DBSCAN and people_kernel read [0, nsel).
+  * ``P``: params_kernel zeroes all P_COUNT slots, then sets n, eps, active, lo / hi, before run_dbscan.
+  * ``lab``: dbscan_labels_kernel writes [0, nsel) before instance_kernel reads lab[pos] (pos < nsel) and lab[i < nsel].
+  * ``laball``: instance_kernel writes [0, nsel) before people_kernel reads as many rows (scal's S_NIN = nsel).
+  * ``scal``, ``offs``: params_kernel writes status, S_NIN and the offsets before people_kernel reads those slots.
+  * ``ptmp``: people_kernel writes k centroids before people_out_kernel copies min(k, cap) of them.
+Tracking (track.hip carve_track, flow_cells; track_history.hip)
+  * ``fwd``, ``bwd``: nearest_kernel writes every row q < cap of both sides of every pair it is launched for,
+    indexed by the pair's start frame; link_kernel / link_open_kernel read the rows of those frames only (frame 0
+    of the batch form, the frames below max(carry, g) of pass g, have no pair and are not read).
+  * ``flag``: link_kernel (batch: every row) or flag_stream_kernel (stream: the rows >= carry * cap) writes nnew
+    entries before the scan reads them; ``partial``, ``rank``: as in DBSCAN's scan, before id_kernel reads rank.
+  * ``idbase`` (stream form): init_stream_kernel copies *ntracks into it before id_kernel adds the rank's total.
+  * flow cells ``cell`` int32[T * cap]: cell_kernel writes every row (-1 for the unmatched) before
+    flow_accumulate_kernel reads all of them.
+  * history ``next`` int32[T * cap]: init_kernel writes kNone from row max(0, carry - 8) * cap on, the only rows a
+    claim can name, before claim_kernel's atomicMin and the walkers' reads.
+
+Wall time per test on the MI355X (pytest --durations): a case takes 0.01 to 0.45 s (test_track_history 0.33 to 0.45 s,
+the application chain 0.11 to 0.35 s, the 298 000-point FPS frame 0.08 s); the first case of a process pays 0.1 to
+0.25 s more for loading the diagnostic library, and test_radius_count[0.5] 1.6 s when it is the first to import
+scikit-learn.  In a run of the whole suite none of this file's cases is among the 80 slowest (all below 0.11 s).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import class_people_reference as cref
+import track_events_reference as eref
+import track_history_reference as href
+import track_reference as tref
+import track_stream_reference as sref
+from diag_lib import diag_library
+from golden_cases import ERROR_FRAMES, FRAMES, META, VFRAMES, check_tier_r, check_variant
+from oracle import tier_n, tier_r
+
+torch = pytest.importorskip("torch")
+from lidar_ai_recommendation_software_amd import _native as nat  # noqa: E402
+from lidar_ai_recommendation_software_amd import data_processing as dp  # noqa: E402
+from lidar_ai_recommendation_software_amd import density_abi as abi  # noqa: E402
+from lidar_ai_recommendation_software_amd import people_tracking as pt  # noqa: E402
+from lidar_ai_recommendation_software_amd import pointnet2 as pn  # noqa: E402
+from lidar_ai_recommendation_software_amd import variant_pipeline as vp  # noqa: E402
+from lidar_ai_recommendation_software_amd.synthetic import lattice_frame, uniform_frame, unit_frames  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+POISON_BYTES = 64 << 20
+
+SENTINEL = {torch.int32: -1515870811, torch.int64: -6510615555426900571, torch.uint8: 0xA5,
+            torch.float32: -1.25e30, torch.float64: -1.25e300}
+NP_OF = {torch.int32: np.int32, torch.int64: np.int64, torch.uint8: np.uint8, torch.float32: np.float32,
+         torch.float64: np.float64}
+
+
+@pytest.fixture
+def diag(cuda):
+    with diag_library(device=cuda.index, poison_bytes=POISON_BYTES) as ctx:
+        yield ctx
+
+
+class Out:
+    """An output buffer of `total` elements (at least the shape's) filled with the dtype's sentinel; `t` is the
+    prefix view the call gets."""
+
+    def __init__(self, shape, dtype, total, dev):
+        self.n = int(np.prod(shape))
+        self.flat = torch.full((max(self.n, int(total)) + 64,), SENTINEL[dtype], dtype=dtype, device=dev)
+        self.t = self.flat[:self.n].view(shape)
+
+    def host(self):
+        return self.t.cpu().numpy()
+
+    def tail_intact(self):
+        return bool(held(self.flat[self.n:].cpu().numpy()).all())
+
+
+def held(a):
+    """Which elements of the host array still hold their dtype's sentinel."""
+    s = {np.dtype(v): SENTINEL[k] for k, v in NP_OF.items()}[a.dtype]
+    return a == np.array(s, dtype=a.dtype)
+
+
+def slack_in(a, total, dev, pad=0.5):
+    """The host array on the device as the prefix of a buffer of `total` elements, the rest finite padding."""
+    a = np.array(a, order="C")  # a writable copy: the planted frames are read-only
+    dtype = torch.from_numpy(a.reshape(-1)[:0].copy()).dtype
+    flat = torch.full((max(a.size, int(total)) + 64,), pad if dtype.is_floating_point else 0, dtype=dtype, device=dev)
+    flat[:a.size] = torch.from_numpy(a.reshape(-1)).to(dev)
+    return flat[:a.size].view(a.shape)
+
+
+def same_bits(got, clean, what):
+    assert got.keys() == clean.keys()
+    for name in got:
+        g, c = np.asarray(got[name]), np.asarray(clean[name])
+        assert g.dtype == c.dtype and g.shape == c.shape and g.tobytes() == c.tobytes(), \
+            f"{what}: {name} differs from the clean handle's"
+
+
+def drive(ctx, run, check, bound, same, shrink, other):
+    """run() -> {name: host array} of the call under test on the current handle; check(out, what) holds it to the
+    oracle and the sentinels.  The clean-handle result first, then the five dirt regimes on the context's handle."""
+    bound = max(1, int(bound))
+    with ctx.clean_handles():
+        clean = run()
+    check(clean, "clean handle")
+    ctx.poison(bound, 7)  # the block at its fixed size from here on
+    regimes = [("poison, seed 1", lambda: ctx.poison(bound, 1), True), ("poison, seed 2", lambda: ctx.poison(bound, 2), True),
+               ("same layout", same, False), ("shrink", shrink, False), ("other operator", other, False)]
+    for what, dirty, poisoned in regimes:
+        if not poisoned:
+            ctx.poison(bound, 3)  # the dirtying call's real data on top of poison, never on zeroed pages
+        dirty()
+        p0, b0, w0 = ctx.info(bound)
+        out = run()
+        p1, b1, w1 = ctx.info(bound)
+        assert p0 != 0 and b0 >= POISON_BYTES and (p0, b0) == (p1, b1), f"{what}: the block moved or grew: " \
+            f"{p0:#x} + {b0} before, {p1:#x} + {b1} after"
+        if poisoned:
+            assert w0 >= b0 // 8 and w1 < w0, f"{what}: {w0} poisoned words before the call, {w1} after"
+        check(out, what)
+        same_bits(out, clean, what)
+
+
+# ---------------------------------------------------------------------------------------------- dirtying calls
+def dirty_fps(dev, B, n, m, seed, threads=0):
+    pn.farthest_point_sample(torch.from_numpy(unit_frames(B, n, seed)).to(dev), m, threads=threads)
+
+
+def dirty_bq(dev, B, n, m, r, ns, seed):
+    x = torch.from_numpy(unit_frames(B, n, seed)).to(dev)
+    pn.ball_query(r, ns, x, x[:, :m].contiguous(), mode="grid")
+
+
+def dirty_dbscan(dev, n, eps, seed):
+    x = torch.from_numpy(np.ascontiguousarray(uniform_frame(n, seed, -1.0, 1.0))).to(dev)
+    lab = torch.empty(n, dtype=torch.int64, device=dev)
+    nat.call("lidar_dbscan_f64", nat.handle(dev.index), nat.ptr(x), n, float(eps), 5, nat.ptr(lab), None, nat.stream_ptr())
+
+
+def dirty_track(dev, T, cap, seed):
+    rng = np.random.default_rng(seed)
+    people = torch.from_numpy(rng.uniform(0.0, 8.0, (T, cap, 2))).to(dev)
+    k = torch.from_numpy(rng.integers(cap // 2, cap + 1, T).astype(np.int64)).to(dev)
+    pt.track_people(people, k, 0.1, 0.5)
+
+
+def dirty_hist(dev, n, bins, seed):
+    p = uniform_frame(n, seed)
+    dp.histogram2d(p[:, 0], p[:, 1], bins=bins)
+
+
+# ---------------------------------------------------------------------------------------------- FPS
+def _fps_case(ctx, dev, kind, B, n, n_big, m, threads):
+    from test_gpu_tier_n import frames_for
+    x = frames_for(kind, B, n, 11)
+    want = tier_n.fps(x, m)
+    want_xyz = np.take_along_axis(x, want[..., None].astype(np.int64), 1)
+    rows = B * n_big
+    xt = slack_in(x, rows * 3, dev)
+
+    def run():
+        idx, nx = Out((B, m), torch.int32, rows, dev), Out((B, m, 3), torch.float32, rows * 3, dev)
+        pn.farthest_point_sample(xt, m, return_xyz=True, out_idx=idx.t, out_xyz=nx.t, threads=threads)
+        torch.cuda.synchronize()
+        return {"idx": idx.host(), "xyz": nx.host(), "tails": np.array([idx.tail_intact(), nx.tail_intact()])}
+
+    def check(out, what):
+        bad = np.argwhere(out["idx"] != want)
+        assert bad.size == 0, f"{what}: {len(bad)} indices differ, first {bad[:3].tolist()}"
+        assert out["xyz"].tobytes() == want_xyz.tobytes(), f"{what}: coordinates"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    drive(ctx, run, check, min(B, n, m),
+          same=lambda: dirty_fps(dev, B, n, m, 12, threads),
+          shrink=lambda: dirty_fps(dev, B, n_big, m, 13, threads),  # the same padded size: real rows where this call's sentinels go
+          other=lambda: dirty_dbscan(dev, min(n, 4000) // 2, 0.2, 14))
+
+
+@pytest.mark.parametrize("threads", [0, 512])
+@pytest.mark.parametrize("kind,B,n,n_big,m", [("uniform", 2, 1000, 1023, 64), ("uniform", 2, 4033, 4096, 300),
+                                              ("dups", 2, 1000, 1023, 64), ("nonfinite", 2, 1000, 1023, 64)])
+def test_fps(diag, cuda, kind, B, n, n_big, m, threads):
+    """n and n_big share one padded bucket count (1 024, 4 096): after the larger frame, real points and distances
+    lie exactly where this call's sentinel tail belongs."""
+    _fps_case(diag, cuda, kind, B, n, n_big, m, threads)
+
+
+def test_fps_large_frame(diag, cuda):
+    """The large-frame kernel (buckets of 1 024 points): 298 000 after 299 008, one padded size."""
+    _fps_case(diag, cuda, "uniform", 1, 298000, 299008, 32, 0)
+
+
+# ---------------------------------------------------------------------------------------------- ball query
+@pytest.mark.parametrize("frame,r,ns", [("uniform", 0.1, 32), ("uniform", 0.3, 128), ("clump", 0.1, 32),
+                                        ("all_equal", 0.1, 32)])
+def test_ball_query_grid(diag, cuda, frame, r, ns):
+    """mode="grid" without a caller grid: the binning goes into the handle."""
+    from test_gpu_tier_n import _bq_edge_frames
+    n, n_big = 6000, 6400
+    if frame == "uniform":
+        x = unit_frames(2, n, 5)
+        c = x[:, :300].copy()
+        c[:, :3] += 3.0  # centres with no neighbour at all: all-zero rows
+    else:
+        x = _bq_edge_frames()[frame][None]
+        c = np.ascontiguousarray(np.concatenate([x[:, :300:3], x[:, :40] + np.float32(7.5), x[:, 40:60] - np.float32(1e7)], 1))
+    B, m = c.shape[:2]
+    want = tier_n.ball_query(x, c, r, ns)
+    xt, ct = slack_in(x, B * n_big * 3, cuda), slack_in(c, B * n_big * 3, cuda)
+
+    def run():
+        idx = Out((B, m, ns), torch.int32, B * m * ns + B * n_big, cuda)
+        pn.ball_query(r, ns, xt, ct, out=idx.t, mode="grid")
+        torch.cuda.synchronize()
+        return {"idx": idx.host(), "tails": np.array([idx.tail_intact()])}
+
+    def check(out, what):
+        assert np.array_equal(out["idx"], want), f"{what}: {(out['idx'] != want).sum()} indices differ"
+        assert out["tails"].all(), f"{what}: written past the output"
+
+    drive(diag, run, check, min(B, m, ns),
+          same=lambda: dirty_bq(cuda, B, n, m, r, ns, 6),
+          shrink=lambda: dirty_bq(cuda, B, n_big, m, r, ns, 7),  # no padding to share: a larger call
+          other=lambda: dirty_fps(cuda, B, 1000, 32, 8))
+
+
+# ---------------------------------------------------------------------------------------------- voxel, single frame
+@pytest.mark.parametrize("n", [3000, 20000])
+def test_voxel_single_frame(diag, cuda, n):
+    v, n_big = 0.05, n + 500
+    x = uniform_frame(n, 3, -1, 1).astype(np.float32)
+    x[n // 2:] = x[: n - n // 2]  # duplicated points share voxels
+    wc, wvid, wcnt = tier_n.voxel_downsample(x, v)
+    xt = slack_in(x, n_big * 3, cuda)
+
+    def voxel(xd, rows, total):
+        vid, cnt = Out((rows,), torch.int32, total, cuda), Out((rows,), torch.int32, total, cuda)
+        cent = Out((rows, 3), torch.float32, total * 3, cuda)
+        nv = nat.I64(0)
+        nat.call("lidar_voxel_downsample_f32", nat.handle(cuda.index), nat.ptr(xd), rows, v, nat.ptr(vid.t), nat.ptr(cent.t),
+                 nat.ptr(cnt.t), ctypes.byref(nv), nat.stream_ptr())
+        torch.cuda.synchronize()
+        return vid, cent, cnt, nv.value
+
+    def run():
+        vid, cent, cnt, nv = voxel(xt, n, n_big)
+        return {"vid": vid.host(), "cent": cent.host()[:nv], "cnt": cnt.host()[:nv], "nvox": np.array(nv),
+                "tails": np.array([vid.tail_intact(), cent.tail_intact(), cnt.tail_intact()])}
+
+    def check(out, what):
+        assert out["nvox"] == len(wc), f"{what}: {out['nvox']} voxels, the oracle has {len(wc)}"
+        assert np.array_equal(out["vid"], wvid) and np.array_equal(out["cnt"], wcnt), what
+        assert out["cent"].tobytes() == wc.tobytes(), f"{what}: centroids"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    def other_data(rows, seed):
+        voxel(torch.from_numpy(uniform_frame(rows, seed, -1, 1).astype(np.float32)).to(cuda), rows, rows)
+
+    drive(diag, run, check, min(n, len(wc)), same=lambda: other_data(n, 4), shrink=lambda: other_data(n_big, 5),
+          other=lambda: dirty_dbscan(cuda, n // 2, 0.2, 6))
+
+
+# ---------------------------------------------------------------------------------------------- DBSCAN, radius count
+def _dbscan_frames(case, seed):
+    """(frame, a frame of more points for the shrink regime, eps)"""
+    if case in ("lattice_0.5", "lattice_0.05"):
+        def frame(s, noise):
+            x = lattice_frame(4, 200, noise, s, 3.0, 0.3)
+            x[: len(x) // 10] = x[len(x) // 10: 2 * (len(x) // 10)]  # duplicates: zero distances
+            return x
+        big = frame(seed + 1, 300)  # the generator draws its blob sizes: 2 000 more rows make it the larger frame for sure
+        return frame(seed, 300), np.concatenate([big, big[:2000] + 0.01]), float(case.split("_")[1])
+    if case == "scan_edge_4097":  # test_dbscan_scan_block_edge_vs_oracle's frame: n + 1 entries cross a scan block
+        def frame(n, s):
+            rng = np.random.default_rng(s)
+            x = np.concatenate([rng.normal(0.0, 0.3, (n // 2, 3)), rng.normal(0.0, 0.3, (n // 4, 3)) + [4.0, 0.0, 0.0],
+                                rng.uniform([-1.5, -1.5, -1.0], [5.5, 1.5, 1.0], (n - n // 2 - n // 4, 3))])
+            x = rng.permutation(x)
+            x[-(n // 16):] = x[:n // 16]
+            return x
+        return frame(4097, 4097 + seed), frame(4500, 1 + seed), 0.25
+    assert case == "coarse_two_far"  # test_dbscan_coarse_grid_path_vs_oracle's: the fine grid exceeds the cell cap
+
+    def far(s, noise):
+        x = lattice_frame(3, 60, noise, s, 3.0, 0.3)
+        x[::2] += 1e6
+        return x
+    big = far(6 + seed, 100)
+    return far(5 + seed, 100), np.concatenate([big, big[:400] + 0.01]), 0.5
+
+
+@pytest.mark.parametrize("case", ["lattice_0.5", "lattice_0.05", "scan_edge_4097", "coarse_two_far"])
+def test_dbscan(diag, cuda, case):
+    x, x_big, eps = _dbscan_frames(case, 0)
+    x_same = _dbscan_frames(case, 10)[0][:len(x)]
+    x_same = np.concatenate([x_same, x_same[: len(x) - len(x_same)]])  # the generators draw their sizes: exactly n rows
+    n, n_big = len(x), len(x_big)
+    assert n_big > n
+    want, wcnt = tier_r.dbscan_labels(x, eps, 5, return_counts=True)
+    assert want.max() >= 1
+    xt = slack_in(x, n_big * 3, cuda)
+
+    def dbscan(xd, rows, total):
+        lab, cnt = Out((rows,), torch.int64, total, cuda), Out((rows,), torch.int32, total, cuda)
+        nat.call("lidar_dbscan_f64", nat.handle(cuda.index), nat.ptr(xd), rows, eps, 5, nat.ptr(lab.t), nat.ptr(cnt.t),
+                 nat.stream_ptr())
+        return lab, cnt
+
+    def run():
+        lab, cnt = dbscan(xt, n, n_big)
+        return {"labels": lab.host(), "counts": cnt.host(), "tails": np.array([lab.tail_intact(), cnt.tail_intact()])}
+
+    def check(out, what):
+        assert np.array_equal(out["counts"], wcnt), f"{what}: neighbour counts"
+        bad = np.flatnonzero(out["labels"] != want)
+        assert bad.size == 0, f"{what}: {bad.size} labels differ, first at {bad[:5]}"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    drive(diag, run, check, min(n, int(want.max()) + 1),
+          same=lambda: dbscan(torch.from_numpy(np.ascontiguousarray(x_same)).to(cuda), n, n),
+          shrink=lambda: dbscan(torch.from_numpy(np.ascontiguousarray(x_big)).to(cuda), len(x_big), len(x_big)),
+          other=lambda: dirty_track(cuda, 5, 300, 3))
+
+
+@pytest.mark.parametrize("r", [0.5, 0.0])
+def test_radius_count(diag, cuda, r):
+    """r = 0 counts exact duplicates only (a tiny positive cell size inside)."""
+    from sklearn.neighbors import KDTree
+    n, n_big = 4096, 4600
+    x = np.repeat(uniform_frame(n // 4, 4), 4, axis=0)
+    x[::7] += 0.25
+    x = np.ascontiguousarray(x)
+    want = KDTree(x).query_radius(x, r=r, count_only=True)
+    assert want.max() >= 4
+    xt = slack_in(x, n_big * 3, cuda)
+
+    def count(xd, rows, total):
+        out = Out((rows,), torch.int64, total, cuda)
+        nat.call("lidar_radius_count_f64", nat.handle(cuda.index), nat.ptr(xd), rows, r, nat.ptr(out.t), nat.stream_ptr())
+        return out
+
+    def run():
+        out = count(xt, n, n_big)
+        return {"counts": out.host(), "tails": np.array([out.tail_intact()])}
+
+    def check(out, what):
+        assert np.array_equal(out["counts"], want), f"{what}: {(out['counts'] != want).sum()} counts differ"
+        assert out["tails"].all(), f"{what}: written past the output"
+
+    def other_data(rows, seed):
+        count(torch.from_numpy(np.ascontiguousarray(uniform_frame(rows, seed))).to(cuda), rows, rows)
+
+    drive(diag, run, check, min(n, int(want.max())), same=lambda: other_data(n, 5), shrink=lambda: other_data(n_big, 6),
+          other=lambda: dirty_fps(cuda, 2, 1000, 64, 7))
+
+
+# ---------------------------------------------------------------------------------------------- preprocess chain
+PRE_FIELDS = (("mask", torch.uint8, 1), ("colors", torch.float64, 3), ("normals", torch.float64, 3),
+              ("comp", torch.float64, 3), ("labels", torch.int64, 1))
+
+
+def _pre_outputs(rows, rows_big, frames, dev):
+    o = {name: Out((rows,) if w == 1 else (rows, w), dtype, rows_big * w, dev) for name, dtype, w in PRE_FIELDS}
+    o["scal"] = Out((abi.SCALARS,) if frames is None else (frames, abi.SCALARS), torch.float64, 0, dev)
+    return o
+
+
+def _no_stamps(S):
+    """The scalars without slots 48 .. 57: the diagnostic build (-DLIDAR_PRE_DIAG) keeps shader-clock stamps of
+    preprocess_kernel's sections there (csrc/tier_r.hpp), which differ from run to run."""
+    S = S.copy()
+    S[..., 48:58] = 0.0
+    return S
+
+
+def _grid_record(dev, people_t, k, S, g, pad=0):
+    """lidar_density_grid_f64 over the first k rows of people_t on the frame's extent -> (host pieces, tails);
+    pad: elements of slack behind each output"""
+    x_min, x_max, y_min, y_max = (float(v) for v in abi.xy_extent(S))
+    nx, ny = nat.grid_dims(x_min, x_max, y_min, y_max, g)
+    gx, gy = Out((nx,), torch.float64, nx + pad, dev), Out((ny,), torch.float64, ny + pad, dev)
+    buf = Out((abi.record_doubles(nx, ny, edges=False),), torch.float64, abi.record_doubles(nx, ny, edges=False) + pad, dev)
+    nat.call("lidar_density_grid_f64", nat.handle(dev.index), nat.ptr(people_t), k, x_min, x_max, y_min, y_max, float(g),
+             nx, ny, nat.ptr(gx.t), nat.ptr(gy.t), nat.ptr(buf.t), nat.stream_ptr())
+    _, _, dens, fx, fy, stats, hot = abi.decode_record(buf.host(), nx, ny, edges=False)
+    # stats[6:8] and the hotspot slots past stats[3] are not part of the record: left out of every comparison
+    return ({"grid_x": gx.host(), "grid_y": gy.host(), "density": dens, "flat_x": fx, "flat_y": fy, "stats": stats[:6].copy(),
+             "hot": hot.copy()}, [gx.tail_intact(), gy.tail_intact(), buf.tail_intact()])
+
+
+def _frame_pieces(o, S, lo, people, k):
+    """The reference-shaped triple (processed_data, people, analyze pieces) of the frame whose rows start at lo."""
+    nin = int(S[abi.S_N_IN])
+    sl = slice(lo, lo + nin)
+    pd = {"points": o["comp"][sl], "colors": o["colors"][sl], "normals": o["normals"][sl], "clusters": o["labels"][sl],
+          "ground_plane": abi.ground_plane(S, False), "dimensions": abi.dimensions(S, None)}
+    return pd, (people[:k] if k else np.array([]))
+
+
+def _check_golden(name, pd, people, rec, k, S, what):
+    res = abi.analyze_result(k, rec["density"], rec["flat_x"], rec["flat_y"], rec["stats"], rec["hot"]) if k else abi.empty_result()
+    check_tier_r(name, pd, people, lambda: res)
+    want = META["cases"][name]["n_clusters"]
+    assert S[abi.S_N_CLUSTERS] == want, f"{what}: {name} reports {S[abi.S_N_CLUSTERS]} clusters, the reference has {want}"
+
+
+def _drop_in(dev, pts, rows_big, g=1.0, eps=None):
+    """preprocess -> people -> density grid of one frame, every output pre-filled -> {name: host array}.  eps: the
+    fixed-eps variant's entry point (lidar_preprocess_eps_batch_f64, one frame) and no grid (the variant's own, a
+    radius density per cell, takes no workspace)."""
+    n = len(pts)
+    x = slack_in(np.ascontiguousarray(pts, dtype=np.float64), rows_big * 3, dev)
+    o = _pre_outputs(n, rows_big, None, dev)
+    h = nat.handle(dev.index)
+    abi.preprocess(h, x, None, 1, n, eps, {name: b.t for name, b in o.items()}, nat.stream_ptr())
+    S = _no_stamps(o["scal"].host())
+    assert S[abi.S_STATUS] == abi.STATUS_OK
+    nin = int(S[abi.S_N_IN])
+    people = Out((n, 2), torch.float64, rows_big * 2, dev)
+    _, k = abi.people(h, o["comp"].t, o["labels"].t, nin, nat.stream_ptr(), out=people.t)
+    out = {name: o[name].host()[:nin] for name in ("colors", "normals", "comp", "labels")}
+    out.update(mask=o["mask"].host(), scal=S, people=people.host()[:k], k=np.array(k))
+    tails = [b.tail_intact() for b in o.values()] + [people.tail_intact()]
+    if k and eps is None:
+        rec, t = _grid_record(dev, people.t, k, S, g)
+        out.update(rec)
+        tails += t
+    out["tails"] = np.array(tails)
+    return out
+
+
+@pytest.mark.parametrize("name", ["small_12", "small_40", "lattice_4293_s0", "uniform_4096_s0"])
+def test_preprocess_drop_in(diag, cuda, name):
+    """The single-frame chain on the smallest goldens: small_12 has fewer than 11 non-ground points (DBSCAN skipped,
+    every non-ground point label 0: one cluster in the scalars), small_40 runs DBSCAN and finds none."""
+    pts = FRAMES[name]()
+    n, n_big = len(pts), len(pts) + 300
+
+    def run():
+        return _drop_in(cuda, pts, n_big)
+
+    def check(out, what):
+        k = int(out["k"])
+        o = {"comp": out["comp"], "colors": out["colors"], "normals": out["normals"], "labels": out["labels"]}
+        pd, people = _frame_pieces(o, out["scal"], 0, out["people"], k)
+        _check_golden(name, pd, people, out, k, out["scal"], what)
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    drive(diag, run, check, n,
+          same=lambda: _drop_in(cuda, uniform_frame(n, 77), n),
+          shrink=lambda: _drop_in(cuda, uniform_frame(n_big, 78), n_big),
+          other=lambda: dirty_hist(cuda, min(n, 1000), 3, 79))  # n >= 12: at most 9 cells
+
+
+@pytest.mark.parametrize("name", ["small_12", "uniform_4096_s0", "lattice_8163_s4"])
+def test_preprocess_eps_variant(diag, cuda, name):
+    """The fixed-eps variant's entry point (the third into run_preprocess) on the variant goldens: small_12 (DBSCAN
+    skipped), the smallest uniform case (nobody found) and the smallest lattice (75 people; the variant goldens have
+    no small_40).  The outputs, pre-filled and with slack like the drop-in's, are held to the goldens through the
+    variant's host oracle: check_variant on the device's processed_data and what oracle.tier_r's analyze makes of it
+    (the counts, densities and hotspots follow from the points and labels alone), and the people against
+    oracle.tier_r's centroids of the same labels."""
+    pts = VFRAMES[name]()
+    n, n_big = len(pts), len(pts) + 300
+
+    def run():
+        return _drop_in(cuda, pts, n_big, eps=vp.EPS)
+
+    def check(out, what):
+        S = out["scal"]
+        pd = {"points": out["comp"], "colors": out["colors"], "clusters": out["labels"], "dimensions": abi.dimensions(S, None)}
+        check_variant(name, pd, tier_r.variant_analyze_crowd_density(pd))
+        want = np.asarray(tier_r.extract_people_positions(pd), dtype=np.float64).reshape(-1, 2)
+        assert int(out["k"]) == len(want) and np.array_equal(out["people"], want), f"{what}: people"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    drive(diag, run, check, n,
+          same=lambda: _drop_in(cuda, uniform_frame(n, 81), n, eps=vp.EPS),
+          shrink=lambda: _drop_in(cuda, uniform_frame(n_big, 82), n_big, eps=vp.EPS),
+          other=lambda: dirty_hist(cuda, min(n, 1000), 3, 83))
+
+
+def drive_pairs(ctx, run, check, bound, same, shrink, other):
+    """drive() for a run() that returns (bits dict, the objects its check needs...)."""
+    keep = {}
+
+    def run_bits():
+        r = run()
+        keep[id(r[0])] = r
+        return r[0]
+
+    drive(ctx, run_bits, lambda bits, what: check(keep[id(bits)], what), bound, same, shrink, other)
+
+
+def _batch(dev, frames, rows_big, g=1.0):
+    """preprocess_batch -> people_batch -> density_batch over the frames on the current handle, every output
+    pre-filled, nothing raised for a failing frame -> {name: host array}."""
+    F = len(frames)
+    sizes = [len(f) for f in frames]
+    offs_h = np.zeros(F + 1, dtype=np.int64)
+    offs_h[1:] = np.cumsum(sizes)
+    rows, max_n = int(offs_h[-1]), max(sizes)
+    x = slack_in(np.ascontiguousarray(np.concatenate(frames), dtype=np.float64), rows_big * 3, dev)
+    offs = torch.from_numpy(offs_h).to(dev)
+    o = _pre_outputs(rows, rows_big, F, dev)
+    h = nat.handle(dev.index)
+    abi.preprocess(h, x, offs, F, max_n, None, {name: b.t for name, b in o.items()}, nat.stream_ptr())
+    people = Out((rows, 2), torch.float64, rows_big * 2, dev)
+    kdev = Out((F,), torch.int64, 0, dev)
+    nat.call("lidar_people_batch_f64", h, nat.ptr(o["comp"].t), nat.ptr(o["labels"].t), nat.ptr(offs), F, max_n,
+             nat.ptr(o["scal"].t), nat.ptr(people.t), nat.ptr(kdev.t), nat.stream_ptr())
+    S, K = _no_stamps(o["scal"].host()), kdev.host()
+    jobs = np.zeros((F, 8), dtype=np.float64)
+    dims, out_off, scr_off = [None] * F, 0, 0
+    for f in range(F):
+        if S[f, abi.S_STATUS] != abi.STATUS_OK or K[f] <= 0:
+            continue
+        x_min, x_max, y_min, y_max = abi.xy_extent(S[f])
+        nx, ny = nat.grid_dims(x_min, x_max, y_min, y_max, g)
+        jobs[f] = abi.job_row(x_min, y_min, g, nx, ny, out_off, scr_off)
+        dims[f] = (nx, ny, out_off)
+        out_off += abi.record_doubles(nx, ny, True)
+        scr_off += abi.scratch_doubles(nx, ny)
+    out = {"mask": o["mask"].host(), "scal": S, "k": K}
+    tails = [b.tail_intact() for b in o.values()] + [people.tail_intact(), kdev.tail_intact()]
+    if out_off:
+        rec = Out((out_off,), torch.float64, 0, dev)
+        jd = torch.from_numpy(jobs).to(dev)  # named: the launch is asynchronous, the tensor must outlive it
+        nat.call("lidar_density_batch_f64", h, nat.ptr(people.t), nat.ptr(offs), nat.ptr(kdev.t), F, nat.ptr(jd),
+                 nat.ptr(rec.t), scr_off, nat.stream_ptr())
+        ob = rec.host()
+        tails.append(rec.tail_intact())
+    host = {name: o[name].host() for name in ("colors", "normals", "comp", "labels")}
+    ph = people.host()
+    for f in range(F):
+        lo, nin = int(offs_h[f]), int(S[f, abi.S_N_IN]) if S[f, abi.S_STATUS] == abi.STATUS_OK else 0
+        for name in host:
+            out[f"{name}{f}"] = host[name][lo:lo + nin]
+        k = int(K[f]) if S[f, abi.S_STATUS] == abi.STATUS_OK else 0
+        out[f"people{f}"] = ph[lo:lo + k]
+        if dims[f] is not None:
+            nx, ny, off = dims[f]
+            gx, gy, dens, fx, fy, stats, hot = abi.decode_record(ob, nx, ny, True, off)
+            out.update({f"grid_x{f}": gx, f"grid_y{f}": gy, f"density{f}": dens, f"flat_x{f}": fx, f"flat_y{f}": fy,
+                        f"stats{f}": stats[:6].copy(), f"hot{f}": hot.copy()})
+    out["tails"] = np.array(tails)
+    return out
+
+
+@pytest.mark.parametrize("order", [("lattice_4293_s0", "small_40", "uniform_4096_s0"),
+                                   ("small_40", "uniform_4096_s0", "lattice_4293_s0"),
+                                   ("uniform_4096_s0", "const_col", "small_12")])
+def test_preprocess_density_batch(diag, cuda, order):
+    """Three unequal frames in one batch, the largest first and then last (every slice is sized for the largest, so
+    the smaller frames' slice tails differ), and a failing frame (const_col: no inlier) between two good ones."""
+    frames = [(FRAMES.get(name) or ERROR_FRAMES[name])() for name in order]
+    rows = sum(len(f) for f in frames)
+    rows_big = rows + 3 * 300
+
+    def run():
+        return _batch(cuda, frames, rows_big)
+
+    def check(out, what):
+        lo = 0
+        for f, name in enumerate(order):
+            S = out["scal"][f]
+            if name in ERROR_FRAMES:
+                assert S[abi.S_STATUS] not in (abi.STATUS_OK, abi.STATUS_EMPTY) and S[abi.S_N_CLUSTERS] == 0, f"{what}: frame {f}"
+                assert f"density{f}" not in out
+                continue
+            assert S[abi.S_STATUS] == abi.STATUS_OK, f"{what}: frame {f}"
+            k = int(out["k"][f])
+            o = {key: out[f"{key}{f}"] for key in ("comp", "colors", "normals", "labels")}
+            pd, people = _frame_pieces(o, S, 0, out[f"people{f}"], k)
+            rec = {key: out.get(f"{key}{f}") for key in ("density", "flat_x", "flat_y", "stats", "hot")}
+            _check_golden(name, pd, people, rec, k, S, f"{what}: frame {f}")
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    sizes = [len(f) for f in frames]
+    drive(diag, run, check, min(len(frames), min(sizes)),
+          same=lambda: _batch(cuda, [uniform_frame(n, 90 + i) for i, n in enumerate(sizes)], rows),
+          shrink=lambda: _batch(cuda, [uniform_frame(n + 300, 94 + i) for i, n in enumerate(sizes)], rows_big),
+          other=lambda: dirty_hist(cuda, 100, 3, 97))
+
+
+# ---------------------------------------------------------------------------------------------- people, density, histogram
+@pytest.mark.parametrize("g", [1.0, 3.7])
+def test_people_density_histogram(diag, cuda, g):
+    """test_people_and_density_on_foreign_input's processed_data (not produced by this library) through
+    lidar_people_f64, lidar_density_grid_f64, lidar_density_batch_f64 (a frame with nobody between two with people)
+    and lidar_histogram2d_f64, as one call under test: lidar_people_f64 alone needs 8 bytes of workspace and leaves
+    the people count there, a value within the poison's range, which the poisoned-word count cannot tell apart."""
+    pds = [tier_r.preprocess_lidar_data(lattice_frame(4, 60, 150, s)) for s in (0, 1)]
+    peoples = [tier_r.extract_people_positions(pd) for pd in pds]
+    n_big = max(len(pd["points"]) for pd in pds) + 300
+    bins = 17
+    hx, hy = pds[0]["points"][:, 0].copy(), pds[0]["points"][:, 1].copy()
+    want_h = np.histogram2d(hx, hy, bins=bins)
+    xe, ye = want_h[1], want_h[2]
+
+    def chain(pd, rows_big):
+        n = len(pd["points"])
+        x = slack_in(pd["points"], rows_big * 3, cuda)
+        lab = slack_in(pd["clusters"], rows_big, cuda)
+        people = Out((n, 2), torch.float64, rows_big * 2, cuda)
+        _, k = abi.people(nat.handle(cuda.index), x, lab, n, nat.stream_ptr(), out=people.t)
+        S = np.zeros(abi.SCALARS)
+        S[abi.S_DIMS:abi.S_DIMS + 4] = pd["dimensions"]["x_range"] + pd["dimensions"]["y_range"]
+        rec, tails = _grid_record(cuda, people.t, k, S, g)
+        return people, k, S, rec, tails + [people.tail_intact()]
+
+    def run():
+        people, k, S, rec, tails = chain(pds[0], n_big)
+        out = dict(rec, people=people.host()[:k], k=np.array(k))
+        # the batch form: frame 0's people, nobody, frame 1's people
+        ks = [k, 0, len(peoples[1])]
+        offs_h = np.array([0, k, k + 4, k + 4 + ks[2]], dtype=np.int64)
+        rows = slack_in(np.concatenate([people.host()[:k], np.full((4, 2), 0.5), peoples[1]]), 2 * n_big, cuda)
+        jobs, dims, out_off, scr_off = np.zeros((3, 8)), {}, 0, 0
+        for f, pd in ((0, pds[0]), (2, pds[1])):
+            (x_min, x_max), (y_min, y_max) = pd["dimensions"]["x_range"], pd["dimensions"]["y_range"]
+            nx, ny = nat.grid_dims(x_min, x_max, y_min, y_max, g)
+            jobs[f] = abi.job_row(x_min, y_min, g, nx, ny, out_off, scr_off)
+            dims[f] = (nx, ny, out_off)
+            out_off += abi.record_doubles(nx, ny, True)
+            scr_off += abi.scratch_doubles(nx, ny)
+        brec = Out((out_off,), torch.float64, 0, cuda)
+        # named tensors: an unnamed one is freed as soon as its pointer is taken, and the next one reuses its memory
+        offs, kd, jd = torch.from_numpy(offs_h).to(cuda), torch.tensor(ks, dtype=torch.int64, device=cuda), torch.from_numpy(jobs).to(cuda)
+        nat.call("lidar_density_batch_f64", nat.handle(cuda.index), nat.ptr(rows), nat.ptr(offs), nat.ptr(kd), 3, nat.ptr(jd),
+                 nat.ptr(brec.t), scr_off, nat.stream_ptr())
+        ob = brec.host()
+        for f, (nx, ny, off) in dims.items():
+            gx, gy, dens, fx, fy, stats, hot = abi.decode_record(ob, nx, ny, True, off)
+            out.update({f"b_grid_x{f}": gx, f"b_grid_y{f}": gy, f"b_density{f}": dens, f"b_flat_x{f}": fx, f"b_flat_y{f}": fy,
+                        f"b_stats{f}": stats[:6].copy(), f"b_hot{f}": hot.copy()})
+        H = Out((bins, bins), torch.float64, 0, cuda)
+        dx, dy, dxe, dye = (torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (hx, hy, xe, ye))
+        nat.call("lidar_histogram2d_f64", nat.handle(cuda.index), nat.ptr(dx), nat.ptr(dy), len(hx), nat.ptr(dxe), bins,
+                 nat.ptr(dye), bins, nat.ptr(H.t), nat.stream_ptr())
+        out["hist"] = H.host()
+        out["tails"] = np.array(tails + [brec.tail_intact(), H.tail_intact()])
+        return out
+
+    def check(out, what):
+        assert np.array_equal(out["people"], peoples[0]), f"{what}: people"
+        for pre, f, pd, ppl in (("", "", pds[0], peoples[0]), ("b_", "0", pds[0], peoples[0]), ("b_", "2", pds[1], peoples[1])):
+            xr, yr = pd["dimensions"]["x_range"], pd["dimensions"]["y_range"]
+            for got, want in zip((out[f"{pre}grid_x{f}"], out[f"{pre}grid_y{f}"], out[f"{pre}density{f}"]),
+                                 tier_r.calculate_grid_density(ppl, xr, yr, g)):
+                assert np.array_equal(got, want), f"{what}: {pre}grid{f}"
+            ra = abi.analyze_result(len(ppl), *(out[f"{pre}{key}{f}"] for key in ("density", "flat_x", "flat_y", "stats", "hot")))
+            rb = tier_r.analyze(pd, g)
+            assert ra["hotspots"] == rb["hotspots"] and ra["avg_density"] == rb["avg_density"], f"{what}: {pre}analyze{f}"
+            assert ra["max_density"] == rb["max_density"] and ra["total_people"] == rb["total_people"], f"{what}: {pre}analyze{f}"
+        assert np.array_equal(out["hist"], want_h[0]), f"{what}: histogram"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    # The dirtying frames have more people than the frame under test, so the count they leave in lidar_people_f64's
+    # word is above the true one: max_label_kernel's atomicMax would keep it if the word were not cleared first.
+    # Same layout: the other lattice frame (19 people against 17); shrink: both frames side by side, relabelled.
+    k0 = len(peoples[0])
+    other_pd = pds[1]
+    shift, relabel = np.array([100.0, 0.0, 0.0]), np.where(pds[1]["clusters"] >= 0, pds[1]["clusters"] + k0, -1)
+    big_pd = {"points": np.concatenate([pds[0]["points"], pds[1]["points"] + shift]),
+              "clusters": np.concatenate([pds[0]["clusters"], relabel]),
+              "dimensions": {"x_range": (pds[0]["dimensions"]["x_range"][0], pds[1]["dimensions"]["x_range"][1] + 100.0),
+                             "y_range": pds[0]["dimensions"]["y_range"]}}
+    assert k0 >= 2 and len(peoples[1]) > k0 and len(big_pd["points"]) > len(pds[0]["points"])
+    assert len(tier_r.extract_people_positions(big_pd)) == k0 + len(peoples[1])
+    drive(diag, run, check, min(k0, bins),
+          same=lambda: chain(other_pd, len(other_pd["points"])),
+          shrink=lambda: chain(big_pd, len(big_pd["points"])),
+          other=lambda: dirty_track(cuda, 3, k0, 5))
+
+
+# ---------------------------------------------------------------------------------------------- class people
+def test_class_people(diag, cuda):
+    """B = 3, n = 2 048: a frame with no selected point, one with every point selected, one with non-finite points;
+    cap below the cluster count, so rows of people past it must stay untouched."""
+    eps, ms, cap = 0.3, 5, 4
+    xyz, labels = (a.copy() for a in cref.planted_frames(*cref.PLANTED_SEG))
+    B, n, _ = xyz.shape
+    labels[0][labels[0] == cref.PERSON] = 0
+    labels[1][:] = cref.PERSON
+    xyz[2, 5::97, 0] = np.nan
+    xyz[2, 7::89, 1] = np.inf
+    xyz[2, 11::83, 2] = -np.inf
+    want = cref.spec_batch(xyz, labels, cref.PERSON, eps, ms)
+    assert want[0]["nsel"] == 0 and want[1]["nsel"] == n and 0 < want[2]["nsel"] < n and want[1]["k"] > cap
+    n_big = 2300
+
+    def call(x, l, rows, rows_big):
+        xt, lt = slack_in(x, B * rows_big * 3, cuda), slack_in(l, B * rows_big, cuda)
+        o = {"instance": Out((B, rows), torch.int32, B * rows_big, cuda), "people": Out((B, cap, 2), torch.float64, B * rows_big * 2, cuda),
+             "k": Out((B,), torch.int64, 0, cuda), "nsel": Out((B,), torch.int64, 0, cuda), "extent": Out((B, 4), torch.float64, 0, cuda)}
+        nat.call("lidar_class_people_f32", nat.handle(cuda.index), nat.ptr(xt), nat.ptr(lt), B, rows, cref.PERSON, eps, ms, cap,
+                 *(nat.ptr(o[name].t) for name in ("instance", "people", "k", "nsel", "extent")), nat.stream_ptr())
+        torch.cuda.synchronize()
+        return o
+
+    def run():
+        o = call(xyz, labels, n, n_big)
+        out = {name: b.host() for name, b in o.items()}
+        out["tails"] = np.array([b.tail_intact() for b in o.values()])
+        return out
+
+    def check(out, what):
+        for f, s in enumerate(want):
+            assert out["nsel"][f] == s["nsel"] and out["k"][f] == s["k"], f"{what}: frame {f} nsel / k"
+            assert np.array_equal(out["extent"][f], s["extent"]), f"{what}: frame {f} extent"
+            bad = np.flatnonzero(out["instance"][f] != s["instance"])
+            assert bad.size == 0, f"{what}: frame {f}: {bad.size} instance labels differ, first at {bad[:5]}"
+            m = min(s["k"], cap)
+            assert np.array_equal(out["people"][f, :m], s["people"][:m]), f"{what}: frame {f} people"
+            assert held(out["people"][f, m:]).all(), f"{what}: frame {f}: people rows past min(k, cap) were written"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    def other_data(rows, seed):
+        x, l = cref.planted_frames(B, rows, seed)
+        call(x, l, rows, rows)
+
+    drive(diag, run, check, min(B, cap), same=lambda: other_data(n, 2), shrink=lambda: other_data(n_big, 3),
+          other=lambda: dirty_fps(cuda, 2, 1000, 64, 4))
+
+
+# ---------------------------------------------------------------------------------------------- tracking
+TRACK_OUT = (("prev", torch.int32, ()), ("track_id", torch.int32, ()), ("velocity", torch.float64, (2,)))
+
+
+def _track_people(dev, people, k, gate, cap_big, T_big):
+    T, cap, _ = people.shape
+    total = T_big * cap_big
+    pd, kd = slack_in(people, total * 2, dev), slack_in(np.asarray(k, dtype=np.int64), T_big, dev)
+    o = {name: Out((T, cap) + tail, dtype, total * (2 if tail else 1), dev) for name, dtype, tail in TRACK_OUT}
+    o["ntracks"] = Out((), torch.int64, 0, dev)
+    nat.call("lidar_track_people_f64", nat.handle(dev.index), nat.ptr(pd), nat.ptr(kd), T, cap, tref.DT, gate,
+             *(nat.ptr(o[name].t) for name in ("prev", "track_id", "velocity", "ntracks")), nat.stream_ptr())
+    torch.cuda.synchronize()
+    out = {name: b.host() for name, b in o.items()}
+    out["tails"] = np.array([b.tail_intact() for b in o.values()])
+    return out
+
+
+def _check_track(out, want, what):
+    for name in ("prev", "track_id"):
+        bad = np.argwhere(out[name] != want[name])
+        assert bad.size == 0, f"{what} {name}: {len(bad)} entries differ, first at {bad[:5].tolist()}"
+    assert out["velocity"].tobytes() == want["velocity"].tobytes(), f"{what}: velocity"
+    assert int(out["ntracks"]) == want["ntracks"], f"{what}: ntracks"
+    assert out["tails"].all(), f"{what}: written past the outputs"
+
+
+@pytest.mark.parametrize("which", ["planted", "one_frame", "k_255_256_257"])
+def test_track_people(diag, cuda, which):
+    """PLANTED[0] (7 frames, cap 43), its first frame alone (no pair: fwd and bwd are never written), and K on both
+    sides of the 256-row workgroup."""
+    gate = 0.25
+    if which == "k_255_256_257":
+        from test_gpu_track import lattice_frames
+        people, k = lattice_frames([255, 256, 257, 256, 255], 257, 11)
+        want = tref.track_spec(people, k, tref.DT, gate)
+    else:
+        people, k = tref.planted_sequence(*tref.PLANTED[0])
+        if which == "one_frame":
+            people, k = people[:1], k[:1]
+        want = tref.track_spec(people, k, tref.DT, gate)
+    T, cap, _ = people.shape
+    T_big, cap_big = T + 2, cap + 10
+    drive(diag, lambda: _track_people(cuda, people, k, gate, cap_big, T_big), lambda out, what: _check_track(out, want, what),
+          min(T, cap, max(1, int(np.min(k)))),
+          same=lambda: dirty_track(cuda, T, cap, 21), shrink=lambda: dirty_track(cuda, T_big, cap_big, 22),
+          other=lambda: dirty_hist(cuda, cap, 2, 23))
+
+
+@pytest.mark.parametrize("max_gap", [0, 2])
+@pytest.mark.parametrize("carry", [0, 1])
+def test_track_stream(diag, cuda, max_gap, carry):
+    """GAPPY[0]; with carry 1 the first frame comes with the state a one-frame call left: its prev, gap, velocity
+    and track_id must come back as given (the specification copies them), succ as the specification sets it."""
+    case, gate = sref.GAPPY[0], 0.5
+    people, k = sref.gappy_sequence(*case)
+    T, cap, _ = people.shape
+    head = sref.stream_spec(people[:1], k[:1], tref.DT, gate, max_gap)
+    state = sref.empty_state(T, cap)
+    for name in sref.STATE:
+        state[name][:1] = head[name]
+    base = head["ntracks"] if carry else 0
+    want = sref.stream_spec(people, k, tref.DT, gate, max_gap, carry, state, base)
+    if max_gap:
+        assert (want["gap"] >= 2).sum() > 0
+    T_big, cap_big = T + 2, cap + 10
+    total = T_big * cap_big
+    layout = pt.state_layout(T, cap)
+
+    def run():
+        pd, kd = slack_in(people, total * 2, cuda), slack_in(np.asarray(k, dtype=np.int64), T_big, cuda)
+        o = {name: Out(shape, dtype, total * (2 if len(shape) == 3 else 1), cuda) for name, dtype, shape in layout}
+        for name in sref.STATE:
+            o[name].t[:carry] = torch.from_numpy(state[name][:carry]).to(cuda)
+        nt = Out((), torch.int64, 0, cuda)
+        nt.t.fill_(base)
+        pt.track_stream(pd, kd, tref.DT, gate, max_gap, carry, tuple(o[name].t for name in sref.STATE), nt.t)
+        torch.cuda.synchronize()
+        out = {name: b.host() for name, b in o.items()}
+        out.update(ntracks=nt.host(), tails=np.array([b.tail_intact() for b in o.values()] + [nt.tail_intact()]))
+        return out
+
+    def check(out, what):
+        for name in sref.STATE:
+            assert out[name].tobytes() == want[name].tobytes(), f"{what}: {name}: {np.argwhere(out[name] != want[name])[:5].tolist()}"
+        assert int(out["ntracks"]) == want["ntracks"], f"{what}: ntracks"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    def other_data(frames, rows, seed):
+        rng = np.random.default_rng(seed)
+        pt.track_stream(torch.from_numpy(rng.uniform(0.0, 6.0, (frames, rows, 2))).to(cuda),
+                        torch.from_numpy(rng.integers(rows // 2, rows + 1, frames).astype(np.int64)).to(cuda), tref.DT, gate, max_gap)
+
+    drive(diag, run, check, min(T, cap, max(1, int(np.min(k)))), same=lambda: other_data(T, cap, 31),
+          shrink=lambda: other_data(T_big, cap_big, 32), other=lambda: dirty_hist(cuda, cap, 2, 33))
+
+
+@pytest.mark.parametrize("form", ["flow_cells", "flow_cells_acc"])
+def test_flow_cells(diag, cuda, form):
+    """flow_cells overwrites the grid; the _acc form with accumulate on continues a pre-loaded one."""
+    case, gate, g = tref.PLANTED[0], 0.5, 1.0
+    people, k = tref.planted_sequence(*case)
+    s = tref.planted_spec(*case, gate)
+    T, cap, _ = people.shape
+    x0, y0, nx, ny, _, _ = tref.venue_grid(*tref.extent_of(people, k), g)
+    rng = np.random.default_rng(9)
+    pre_c, pre_v = rng.integers(0, 5, (nx, ny)).astype(np.int32), rng.integers(-8, 9, (nx, ny, 2)) / 4.0
+    if form == "flow_cells":
+        want_c, want_v = tref.flow_cells_spec(people, k, s["prev"], s["velocity"], x0, y0, g, nx, ny)
+    else:
+        want_c, want_v = sref.flow_cells_acc_spec(people, k, s["prev"], s["velocity"], x0, y0, g, nx, ny, 1, pre_c, pre_v)
+    assert want_c.sum() > pre_c.sum() * (form != "flow_cells")
+    T_big, cap_big = T + 2, cap + 10
+    total = T_big * cap_big
+
+    def cells(pe, kk, prev, vel, tot):
+        frames, rows, _ = pe.shape
+        pd, kd = slack_in(pe, tot * 2, cuda), slack_in(np.asarray(kk, dtype=np.int64), T_big, cuda)
+        pv, vd = slack_in(prev, tot, cuda), slack_in(vel, tot * 2, cuda)
+        count, vsum = Out((nx, ny), torch.int32, 0, cuda), Out((nx, ny, 2), torch.float64, 0, cuda)
+        if form == "flow_cells":
+            nat.call("lidar_flow_cells_f64", nat.handle(cuda.index), nat.ptr(pd), nat.ptr(kd), nat.ptr(pv), nat.ptr(vd), frames, rows,
+                     x0, y0, g, nx, ny, nat.ptr(count.t), nat.ptr(vsum.t), nat.stream_ptr())
+        else:
+            count.t.copy_(torch.from_numpy(pre_c))
+            vsum.t.copy_(torch.from_numpy(pre_v))
+            nat.call("lidar_flow_cells_acc_f64", nat.handle(cuda.index), nat.ptr(pd), nat.ptr(kd), nat.ptr(pv), nat.ptr(vd), frames,
+                     rows, 1, 1, x0, y0, g, nx, ny, nat.ptr(count.t), nat.ptr(vsum.t), nat.stream_ptr())
+        torch.cuda.synchronize()
+        return {"count": count.host(), "vsum": vsum.host(), "tails": np.array([count.tail_intact(), vsum.tail_intact()])}
+
+    def check(out, what):
+        assert np.array_equal(out["count"], want_c), f"{what}: count"
+        assert out["vsum"].tobytes() == want_v.tobytes(), f"{what}: vsum"
+        assert out["tails"].all(), f"{what}: written past the outputs"
+
+    def other_data(frames, rows, seed):
+        rng2 = np.random.default_rng(seed)
+        pe = rng2.uniform(x0, x0 + nx * g, (frames, rows, 2))
+        kk = rng2.integers(rows // 2, rows + 1, frames)
+        sp = tref.track_spec(pe, kk, tref.DT, gate)
+        cells(pe, kk, sp["prev"], sp["velocity"], frames * rows)
+
+    drive(diag, lambda: cells(people, k, s["prev"], s["velocity"], total), check, min(T, cap, nx * ny),
+          same=lambda: other_data(T, cap, 41), shrink=lambda: other_data(T_big, cap_big, 42),
+          other=lambda: dirty_hist(cuda, cap, 2, 43))
+
+
+def test_track_history(diag, cuda):
+    """The crossing scene (links over missed frames, stays that end) with its three zones."""
+    from test_gpu_track_history import same as same_history
+    max_gap = 2
+    people, k, _, zones = eref.crossing_scene()
+    s = eref.crossing_spec(max_gap)[0]
+    want = href.crossing_history(max_gap)
+    T, cap, _ = people.shape
+    Z = len(zones)
+    T_big, cap_big = T + 2, cap + 10
+    total = T_big * cap_big
+    layout = pt.history_layout(T, cap, Z)
+    zd = torch.from_numpy(np.array(zones)).to(cuda)
+
+    def history(pe, kk, prev, gap, tot, lay):
+        pd, kd = slack_in(pe, tot * 2, cuda), slack_in(np.asarray(kk, dtype=np.int64), T_big, cuda)
+        pv, gd = slack_in(prev, tot, cuda), slack_in(gap, tot, cuda)
+        o = [Out(shape, dtype, tot * int(np.prod(shape[2:])), cuda) for _, dtype, shape in lay]
+        got = pt.track_history(pd, kd, pv, gd, zd, 0, tuple(b.t for b in o))
+        torch.cuda.synchronize()
+        return got, o
+
+    def run():
+        got, o = history(people, k, s["prev"], s["gap"], total, layout)
+        out = {name: np.nan_to_num(t.cpu().numpy(), nan=0.0) if t.dtype == torch.float64 else t.cpu().numpy()
+               for name, t in zip(href.NAMES, got)}  # a NaN's payload and sign are free (test_gpu_track_history.same)
+        out["nan"] = np.concatenate([np.isnan(t.cpu().numpy()).reshape(-1) for t in got if t.dtype == torch.float64])
+        out["tails"] = np.array([b.tail_intact() for b in o])
+        return out, got
+
+    def check(out, what):
+        same_history(out[1], want, what)
+        assert out[0]["tails"].all(), f"{what}: written past the outputs"
+
+    def other_data(frames, rows, seed):
+        rng = np.random.default_rng(seed)
+        pe = rng.uniform(0.0, 6.0, (frames, rows, 2))
+        kk = rng.integers(rows // 2, rows + 1, frames)
+        sp = sref.stream_spec(pe, kk, tref.DT, 0.5, max_gap)
+        history(pe, kk, sp["prev"], sp["gap"], frames * rows, pt.history_layout(frames, rows, Z))
+
+    drive_pairs(diag, run, check, min(T, cap, Z), same=lambda: other_data(T, cap, 51),
+                shrink=lambda: other_data(T_big, cap_big, 52), other=lambda: dirty_hist(cuda, cap, 2, 53))
+
+
+# ---------------------------------------------------------------------------------------------- the application's chain
+CHAIN_PAD = 3 * 16384  # elements of slack behind every buffer of the chain: above rows x width of its largest call
+
+
+def _pad_in(a, dev):
+    return slack_in(a, np.asarray(a).size + CHAIN_PAD, dev)
+
+
+def _pad_out(shape, dtype, dev):
+    return Out(shape, dtype, int(np.prod(shape)) + CHAIN_PAD, dev)
+
+
+def _bits(**named):
+    """{name: host array} of Out buffers and host arrays, NaNs canonical (their payload and sign are free), plus
+    whether every Out's slack still holds the sentinel."""
+    out, tails = {}, []
+    for name, v in named.items():
+        if isinstance(v, Out):
+            tails.append(v.tail_intact())
+            v = v.host()
+        v = np.asarray(v)
+        out[name] = np.nan_to_num(v, nan=0.0) if v.dtype.kind == "f" else v
+    out["tails"] = np.array(tails)
+    return out
+
+
+def _chain_ops(dev, rnd):
+    """The application's operators on round `rnd`'s frames -> [(name, fn)], fn() -> {name: host array} of what the
+    operator's specification defines.  Any operator may follow any other here, so every caller-side buffer, input
+    or output, carries CHAIN_PAD elements of slack (inputs padded with 0.5, outputs with the sentinel) and the call
+    gets the prefix view, through the wrappers' own out= / state= arguments or, where a wrapper allocates its
+    outputs itself, through the entry point."""
+    h = lambda: nat.handle(dev.index)  # noqa: E731
+    pts = [FRAMES["lattice_4293_s0"], FRAMES["blobs_4293_s0"]][rnd]()
+    pd = tier_r.preprocess_lidar_data(pts)
+    ppl = tier_r.extract_people_positions(pd)
+    assert len(ppl) > 3  # the people count the operator leaves in its word is no poison value (bound 3)
+    S_dims = np.zeros(abi.SCALARS)
+    S_dims[abi.S_DIMS:abi.S_DIMS + 4] = pd["dimensions"]["x_range"] + pd["dimensions"]["y_range"]
+    rows_big = CHAIN_PAD // 3
+    x64 = _pad_in(np.ascontiguousarray(pts, dtype=np.float64), dev)
+    px, pl, pp = _pad_in(pd["points"], dev), _pad_in(pd["clusters"], dev), _pad_in(ppl, dev)
+    cloud = _pad_in(unit_frames(2, 3000 + 100 * rnd, 60 + rnd), dev)
+    centres = _pad_in(cloud[:, :200].cpu().numpy(), dev)
+    B, N, _ = cloud.shape
+    cx, cl = cref.planted_frames(2, 2048, 4 + rnd)
+    cxyz, clab = _pad_in(cx, dev), _pad_in(cl, dev)
+    people, k = sref.gappy_sequence(*sref.GAPPY[rnd])
+    T, cap, _ = people.shape
+    sp = sref.gappy_spec(*sref.GAPPY[rnd], 0.5, 2)
+    zones_h = eref.scene_tables(eref.lattice_side(sref.GAPPY[rnd][1]))[1]
+    Z = len(zones_h)
+    pe, kd, zones, prev, gap = (_pad_in(a, dev) for a in (people, np.asarray(k, dtype=np.int64), zones_h, sp["prev"], sp["gap"]))
+
+    def preprocess():
+        n = len(pts)
+        o = _pre_outputs(n, n + rows_big, None, dev)
+        abi.preprocess(h(), x64, None, 1, n, None, {name: b.t for name, b in o.items()}, nat.stream_ptr())
+        S = _no_stamps(o["scal"].host())
+        nin = int(S[abi.S_N_IN])
+        out = _bits(scal=S, **{name: o[name].host()[:nin] for name in ("colors", "normals", "comp", "labels")}, mask=o["mask"])
+        out["tails"] = np.array([b.tail_intact() for b in o.values()])
+        return out
+
+    def people_op():
+        n = len(pd["points"])
+        out = _pad_out((n, 2), torch.float64, dev)
+        _, kk = abi.people(h(), px, pl, n, nat.stream_ptr(), out=out.t)
+        res = _bits(people=out.host()[:kk], k=np.array(kk))
+        res["tails"] = np.array([out.tail_intact()])
+        return res
+
+    def density_grid():
+        rec, tails = _grid_record(dev, pp, len(ppl), S_dims, 1.0, CHAIN_PAD)
+        return dict(rec, tails=np.array(tails))
+
+    def voxel():
+        cent, vid, cnt = _pad_out((B, N, 3), torch.float32, dev), _pad_out((B, N), torch.int32, dev), _pad_out((B, N), torch.int32, dev)
+        nv = _pad_out((B,), torch.int32, dev)
+        pn.voxel_downsample_batch(cloud, 0.05, out=(cent.t, vid.t, cnt.t, nv.t))
+        nvh = nv.host()
+        out = _bits(vid=vid, nvox=nv, **{f"cent{f}": cent.host()[f, :v] for f, v in enumerate(nvh)},
+                    **{f"cnt{f}": cnt.host()[f, :v] for f, v in enumerate(nvh)})
+        out["tails"] = np.array([b.tail_intact() for b in (cent, vid, cnt, nv)])
+        return out
+
+    def fps():
+        idx, nx = _pad_out((B, 128), torch.int32, dev), _pad_out((B, 128, 3), torch.float32, dev)
+        pn.farthest_point_sample(cloud, 128, return_xyz=True, out_idx=idx.t, out_xyz=nx.t)
+        return _bits(idx=idx, xyz=nx)
+
+    def ball_query():
+        idx = _pad_out((B, 200, 32), torch.int32, dev)
+        pn.ball_query(0.2, 32, cloud, centres, out=idx.t, mode="grid")
+        return _bits(idx=idx)
+
+    def class_people():
+        n = cxyz.shape[1]
+        inst, ppl_d = _pad_out((2, n), torch.int32, dev), _pad_out((2, n, 2), torch.float64, dev)
+        kk, nsel, ext = _pad_out((2,), torch.int64, dev), _pad_out((2,), torch.int64, dev), _pad_out((2, 4), torch.float64, dev)
+        nat.call("lidar_class_people_f32", h(), nat.ptr(cxyz), nat.ptr(clab), 2, n, cref.PERSON, 0.3, 5, n, nat.ptr(inst.t),
+                 nat.ptr(ppl_d.t), nat.ptr(kk.t), nat.ptr(nsel.t), nat.ptr(ext.t), nat.stream_ptr())
+        out = _bits(instance=inst, k=kk, nsel=nsel, extent=ext, **{f"people{f}": ppl_d.host()[f, :v] for f, v in enumerate(kk.host())})
+        out["tails"] = np.array([b.tail_intact() for b in (inst, ppl_d, kk, nsel, ext)])
+        return out
+
+    def track_stream():
+        state = {name: _pad_out(shape, dtype, dev) for name, dtype, shape in pt.state_layout(T, cap)}
+        nt = _pad_out((), torch.int64, dev)
+        nt.t.zero_()
+        pt.track_stream(pe, kd, tref.DT, 0.5, 2, 0, tuple(b.t for b in state.values()), nt.t)
+        return _bits(ntracks=nt, **state)
+
+    def track_history():
+        o = {name: _pad_out(shape, dtype, dev) for name, dtype, shape in pt.history_layout(T, cap, Z)}
+        dwell = _pad_out((T, Z, 3), torch.int64, dev)
+        nat.call("lidar_track_history_f64", h(), nat.ptr(pe), nat.ptr(kd), nat.ptr(prev), nat.ptr(gap), T, cap, 0, nat.ptr(zones), Z,
+                 *(nat.ptr(b.t) for b in o.values()), nat.ptr(dwell.t), nat.stream_ptr())
+        return _bits(dwell=dwell, **o)
+
+    return [("preprocess", preprocess), ("people", people_op), ("density_grid", density_grid), ("voxel", voxel), ("fps", fps),
+            ("ball_query", ball_query), ("class_people", class_people), ("track_stream", track_stream),
+            ("track_history", track_history)]
+
+
+@pytest.mark.parametrize("order_seed", [None, 1, 2])
+def test_application_chain_on_one_handle(diag, cuda, order_seed):
+    """preprocess, people, density grid, voxel, FPS, ball query, class people, track stream, history on one handle,
+    twice over different frames, the block poisoned once between the rounds; in the natural order and two seeded
+    shuffles every result equals the same operator's result on a newly created handle, nothing is written past an
+    output and the block stays where it is.  Before the rounds every operator runs once straight after a poison and
+    must lower the poisoned-word count: each of them really works in this handle's block."""
+    bound = 3
+    rounds = [_chain_ops(cuda, rnd) for rnd in (0, 1)]
+    clean = []
+    for ops in rounds:
+        res = {}
+        for name, fn in ops:
+            with diag.clean_handles():
+                res[name] = fn()
+            assert res[name]["tails"].all(), f"clean handle, {name}: written past the outputs"
+        clean.append(res)
+    diag.poison(bound, 10)
+    block = diag.info(bound)[:2]
+    assert block[0] != 0 and block[1] >= POISON_BYTES
+    for rnd, ops in enumerate(rounds):
+        for name, fn in ops:
+            diag.poison(bound, 20 + rnd)
+            w0 = diag.info(bound)[2]
+            same_bits(fn(), clean[rnd][name], f"after a poison, round {rnd}'s {name}")
+            p1, b1, w1 = diag.info(bound)
+            assert (p1, b1) == block and w1 < w0, f"round {rnd}'s {name}: {w0} poisoned words before the call, {w1} after"
+    diag.poison(bound, 11)
+    for rnd, ops in enumerate(rounds):
+        order = list(range(len(ops)))
+        if order_seed is not None:
+            order = np.random.default_rng(100 * order_seed + rnd).permutation(len(ops)).tolist()
+        if rnd:
+            diag.poison(bound, 12)
+        for i in order:
+            name, fn = ops[i]
+            out = fn()
+            same_bits(out, clean[rnd][name], f"round {rnd}, {name} (order {order})")
+            assert out["tails"].all(), f"round {rnd}, {name}: written past the outputs"
+        assert diag.info(bound)[:2] == block, "the block moved or grew"
