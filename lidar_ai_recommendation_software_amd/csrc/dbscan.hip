@@ -26,7 +26,7 @@ __global__ void dbscan_params_from_preprocess(const double *S_in, DbscanWs w, Fr
     P[P_ACTIVE] = (S[S_STATUS] == 0.0 && nng > 10.0) ? 1.0 : 0.0;
     // dbscan_labels_kernel counts the clusters of an active frame only, and this block lives in the handle's
     // workspace: a frame DBSCAN skips must not report what an earlier call left in the slot.  Its non-ground
-    // points (1 .. 10 of them) all take label 0 (scatter_labels2_kernel): one cluster; a failed frame has none.
+    // points (1 .. 10 of them) all take label 0 (cluster_label_scatter_kernel): one cluster; a failed frame has none.
     P[P_NCLUST] = (S[S_STATUS] == 0.0 && nng >= 1.0) ? 1.0 : 0.0;
     for (int c = 0; c < 3; ++c) {
         P[P_LO + c] = S[S_SLO + c];

@@ -16,17 +16,14 @@ namespace {
 
 using namespace lidar::tier_r;
 
-// deterministic (fixed tree) block sum — used only where the reference itself is not
-// bit-reproducible (the gelsd plane fit)
-__device__ double block_sum(BlockScratch &s, double v, int slot)
+// deterministic block sum (row 2 + SLOT of s.d) — used only where the reference itself is not
+// bit-reproducible (the gelsd plane fit).  Relies on block_reduce's fixed order (the xor butterfly
+// from 32 down to 1 within a wave, then the waves' totals added in wave order): fp64 addition is not
+// associative, so another order is another result
+template <int SLOT>
+__device__ __forceinline__ double block_sum(BlockScratch &s, double v)
 {
-    for (int m = 32; m >= 1; m >>= 1) v = dadd(v, __shfl_xor(v, m, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s.d[2 + slot][threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = s.d[2 + slot][0];
-    for (int w = 1; w < kW; ++w) r = dadd(r, s.d[2 + slot][w]);
-    return r;
+    return block_reduce<2 + SLOT>(s, v, [](double a, double b) { return dadd(a, b); });
 }
 // exclusive scan of a 0/1 flag over the workgroup; returns the position, *total set
 __device__ int block_flag_scan(BlockScratch &s, bool f, int *total)
@@ -49,18 +46,15 @@ __device__ int block_flag_scan(BlockScratch &s, bool f, int *total)
 
 // ---- index-order fp64 chains with the rows streamed through LDS
 // numpy's axis-0 reductions of a row-major (n, 3) array are sequential per column, so the
-// result depends on every rounding in index order.  The rows are staged into LDS in 1024-row
-// chunks (double buffered) by the waves that do not run a chain.  Two ways to run a chain:
-// block_seq_chain, the dependent adds themselves (lanes 0..2 of wave 0, lane c = column c), for
-// sums of signed values (coordinates, deviations: their accumulator wanders across binades near
-// zero), and block_sum_chain below, a parallel emulation, for sums of squares.
-#ifndef LIDAR_SEQ_ROWS
-#define LIDAR_SEQ_ROWS 3072
-#endif
+// result depends on every rounding in index order.  block_staged_rows streams the rows through LDS
+// in chunks; two ways to run a chain on a staged chunk: seq_chain_rows, the dependent adds themselves
+// (one lane per column), for sums of signed values (coordinates, deviations: their accumulator
+// wanders across binades near zero), and sum_chain_rows below, a parallel emulation (one wave per
+// column), for sums of squares.
 // rows per staged chunk: 3 072 (147 KiB double-buffered; the kernel is one 1 024-thread workgroup per CU
 // by its registers anyway): preprocess 2.70 ms per 32 frames vs 2.79 at 2 048 and 2.98 at 1 024
 // (round-3 A/B): fewer chunk barriers, each waiting on the next chunk's staging
-constexpr int kSeqRows = LIDAR_SEQ_ROWS;
+constexpr int kSeqRows = 3072;
 // rows whose LDS reads are issued before their dependent adds (32 measured equal, 64 slower: the
 // chain is bound by the dependent fp64 adds, not by the LDS reads)
 constexpr int kSeqBatch = 16;
@@ -68,9 +62,41 @@ struct SeqStage {
     double v[2][kSeqRows * 3];
 };
 
-// one staged chunk's rows of the index-order chain of column c (lane c of wave 0): b = the chunk's column c
+// rows [0, n) of x (row-major (n, 3)) through LDS in kSeqRows-row chunks, double buffered: the waves
+// 0 .. WORKERS - 1 call work(chunk, rows) on chunk k (every thread of them; they never wait on global
+// loads) while the waves from WORKERS up stage chunk k + 1.  One barrier per chunk; ends with a barrier.
+template <int WORKERS, class Work>
+__device__ __forceinline__ void block_staged_rows(const double *x, int64_t n, SeqStage &st, Work work)
+{
+    constexpr int kWorkT = 64 * WORKERS;  // the first staging thread
+    const int tid = threadIdx.x;
+    const int64_t nch = (n + kSeqRows - 1) / kSeqRows;
+    auto rows_of = [&](int64_t k) { return n - k * kSeqRows < kSeqRows ? n - k * kSeqRows : kSeqRows; };
+    auto stage = [&](int64_t k) {
+        if (tid < kWorkT || k >= nch) return;
+        const int64_t cnt = rows_of(k) * 3;
+        double *d = st.v[k & 1];
+        const double *src = x + 3 * k * kSeqRows;
+        for (int64_t e = tid - kWorkT; e < cnt; e += kT - kWorkT) d[e] = src[e];
+    };
+    // every earlier memory access finished before the first chunk: the workspace pointers (FrameMap::ws goes
+    // through an integer) are flat addresses to the compiler, a flat access counts on the LDS counter too, and
+    // while one may be outstanding (the compaction's and the transform's stores) the compiler makes every LDS
+    // wait of the chains a full one instead of counting a batch's 16 reads down: preprocess 2.64 vs 2.45 ms
+    // per 32 frames
+    __builtin_amdgcn_s_waitcnt(0);
+    stage(0);
+    __syncthreads();
+    for (int64_t k = 0; k < nch; ++k) {
+        stage(k + 1);
+        if (tid < kWorkT) work(st.v[k & 1], (int)rows_of(k));
+        __syncthreads();
+    }
+}
+
+// one staged chunk's rows of an index-order chain a <- step(a, row) (one lane): b = the chunk's column
 template <class Step>
-__device__ __forceinline__ void seq_chain_rows(const double *b, int rows, int c, Step step, double &a0, double &a1)
+__device__ __forceinline__ void seq_chain_rows(const double *b, int rows, Step step, double &a)
 {
     // reads of a 16-row batch first, then its dependent adds (an explicit two-batch
     // software pipeline measured 2.4x slower: 7.6 vs 3.2 ms per 65k frame)
@@ -80,35 +106,21 @@ __device__ __forceinline__ void seq_chain_rows(const double *b, int rows, int c,
 #pragma unroll
         for (int u = 0; u < kSeqBatch; ++u) v[u] = b[3 * (i + u)];
 #pragma unroll
-        for (int u = 0; u < kSeqBatch; ++u) step(c, v[u], a0, a1);
+        for (int u = 0; u < kSeqBatch; ++u) a = step(a, v[u]);
     }
-    for (; i < rows; ++i) step(c, b[3 * i], a0, a1);
+    for (; i < rows; ++i) a = step(a, b[3 * i]);
 }
 
+// the index-order chains of the three columns, a <- step(a, x[i][c]) from a = +0.0, on lanes c = 0..2
+// of wave 0 (waves 1..15 stage): thread c returns column c's result, the others 0
 template <class Step>
-__device__ void block_seq_chain(const double *x, int64_t n, SeqStage &st, Step step, double &a0, double &a1)
+__device__ __forceinline__ double block_seq_chain(const double *x, int64_t n, SeqStage &st, Step step)
 {
-    const int tid = threadIdx.x;
-    const int64_t nch = (n + kSeqRows - 1) / kSeqRows;
-    auto stage = [&](int64_t k) {
-        if (tid < 64 || k >= nch) return;  // wave 0 never waits on global loads
-        const int64_t r0 = k * kSeqRows;
-        const int64_t cnt = (n - r0 < kSeqRows ? n - r0 : kSeqRows) * 3;
-        double *d = st.v[k & 1];
-        const double *src = x + 3 * r0;
-        for (int64_t e = tid - 64; e < cnt; e += kT - 64) d[e] = src[e];
-    };
-    stage(0);
-    __syncthreads();
-    for (int64_t k = 0; k < nch; ++k) {
-        stage(k + 1);
-        if (tid < 3) {
-            const int64_t r0 = k * kSeqRows;
-            const int rows = (int)(n - r0 < kSeqRows ? n - r0 : kSeqRows);
-            seq_chain_rows(st.v[k & 1] + tid, rows, tid, step, a0, a1);
-        }
-        __syncthreads();
-    }
+    double a = 0.0;
+    block_staged_rows<1>(x, n, st, [&](const double *chunk, int rows) {
+        if (threadIdx.x < 3) seq_chain_rows(chunk + threadIdx.x, rows, step, a);
+    });
+    return a;
 }
 
 // ---- the same index-order chains, emulated in parallel, bit for bit
@@ -161,14 +173,10 @@ __device__ __forceinline__ double wave_scan_exact_d(double P)
     return P;
 }
 
-// chain (column c = wave % 3, accumulator q = wave / 3) of rows [0, n) of x (row-major (n, 3)):
-// a_q[c] <- fl(a_q[c] + inc(c, q, x[i][c])).  Waves 0 .. 3 NQ - 1 run the chains; the other waves
-// stage 1024-row chunks into LDS (double buffered).  Results land in s.chain[q * 3 + c] (ends with
-// a barrier).
-// one staged chunk's rows of the emulated chain a <- fl(a + inc(c, q, x_i[c])) (one wavefront; b = the chunk's
-// column c; a and forced carry over from chunk to chunk)
+// one staged chunk's rows of the emulated chain a <- fl(a + inc(row)) (one wavefront; b = the chunk's
+// column; a, from +0.0, and forced, from 0, carry over from chunk to chunk)
 template <class Inc>
-__device__ __forceinline__ void sum_chain_rows(const double *b, int rows, int c, int q, Inc inc, double &a, int &forced)
+__device__ __forceinline__ void sum_chain_rows(const double *b, int rows, Inc inc, double &a, int &forced)
 {
     constexpr double kTwo52 = 4503599627370496.0, kTwo53 = 9007199254740992.0, kTwo44 = 17592186044416.0;
     const int lane = threadIdx.x & 63;
@@ -184,11 +192,11 @@ __device__ __forceinline__ void sum_chain_rows(const double *b, int rows, int c,
             for (; t + 8 <= run; t += 8) {
                 double v[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = inc(c, q, b[3 * (i + t + u)]);
+                for (int u = 0; u < 8; ++u) v[u] = inc(b[3 * (i + t + u)]);
 #pragma unroll
                 for (int u = 0; u < 8; ++u) a = dadd(a, v[u]);
             }
-            for (; t < run; ++t) a = dadd(a, inc(c, q, b[3 * (i + t)]));
+            for (; t < run; ++t) a = dadd(a, inc(b[3 * (i + t)]));
             i += run;
             forced = forced > run ? forced - run : 0;
             continue;
@@ -211,7 +219,7 @@ __device__ __forceinline__ void sum_chain_rows(const double *b, int rows, int c,
         }
 #pragma unroll
         for (int r = 0; r < kChainRowsPerLane; ++r) {
-            v[r] = valid[r] ? inc(c, q, raw[r]) : 0.0;
+            v[r] = valid[r] ? inc(raw[r]) : 0.0;
             const double xs = ldexp(v[r], sh);
             double kq = rint(xs);
             bad[r] = valid[r] && (!(fabs(kq) <= kTwo44) || dsub(xs, floor(xs)) == 0.5);
@@ -261,75 +269,42 @@ __device__ __forceinline__ void sum_chain_rows(const double *b, int rows, int c,
     }
 }
 
-template <int NQ, class Inc>
-__device__ void block_sum_chain(const double *x, int64_t n, SeqStage &st, BlockScratch &s, Inc inc)
-{
-    constexpr int kCW = 3 * NQ;  // chain waves
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t nch = (n + kSeqRows - 1) / kSeqRows;
-    auto stage = [&](int64_t k) {
-        if (wave < kCW || k >= nch) return;  // the chain waves never wait on global loads
-        const int64_t r0 = k * kSeqRows;
-        const int64_t cnt = (n - r0 < kSeqRows ? n - r0 : kSeqRows) * 3;
-        double *d = st.v[k & 1];
-        const double *src = x + 3 * r0;
-        for (int64_t e = tid - 64 * kCW; e < cnt; e += kT - 64 * kCW) d[e] = src[e];
-    };
-    const int c = wave % 3, q = wave / 3;
-    double a = 0.0;
-    int forced = 0;
-    stage(0);
-    __syncthreads();
-    for (int64_t k = 0; k < nch; ++k) {
-        stage(k + 1);
-        if (wave < kCW) {
-            const int64_t r0 = k * kSeqRows;
-            const int rows = (int)(n - r0 < kSeqRows ? n - r0 : kSeqRows);
-            const double *b = st.v[k & 1] + c;
-            sum_chain_rows(b, rows, c, q, inc, a, forced);
-        }
-        __syncthreads();
+struct SqDev {  // the increment of every emulated chain here: the squared deviation from m
+    double m;
+    __device__ double operator()(double v) const
+    {
+        const double d = dsub(v, m);
+        return dmul(d, d);
     }
-    if (wave < kCW && lane == 0) s.chain[q * 3 + c] = a;
-    __syncthreads();
-}
+};
 
-// both kinds at once over the same staged rows: the index-order chain `step` (lanes 0..2 of wave 0, as
-// block_seq_chain) and the emulated chain of `inc` (waves 1..3, column = wave - 1, as block_sum_chain with
-// NQ = 1, result in s.chain[column]); waves 4.. stage.  One pass instead of two, or instead of a step
-// carrying both: the StandardScaler's second pass (its correction sum stays sequential, its sum of
-// squared deviations is emulated beside it)
-template <class Step, class Inc>
-__device__ void block_seq_sum_chain(const double *x, int64_t n, SeqStage &st, BlockScratch &s, Step step, double &a0,
-                                    double &a1, Inc inc)
+// what the phases of preprocess_kernel hand to the whole workgroup through LDS: written by the few
+// threads that computed it, read by all after a barrier
+struct PreShared {
+    double mean[3], std[3];      // col_moments
+    uint64_t sel_prefix[2];      // select_z_threshold: the key digits chosen so far for the two order statistics,
+    int64_t sel_rank[2];         // and each one's rank among the keys that share them
+    double smean[3], sscale[3];  // scaler_fit
+};
+
+// sh.mean, sh.std = np.mean / np.std over axis 0 of the rows [0, n) of x: the mean by the index-order chain
+// (lanes 0..2 of wave 0), then the population standard deviation from the emulated chain of squared
+// deviations (waves 0..2, column = wave; waves 3..15 stage).  Ends with a barrier.
+__device__ __forceinline__ void col_moments(const double *x, int64_t n, SeqStage &st, BlockScratch &s, PreShared &sh)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t nch = (n + kSeqRows - 1) / kSeqRows;
-    auto stage = [&](int64_t k) {
-        if (wave < 4 || k >= nch) return;
-        const int64_t r0 = k * kSeqRows;
-        const int64_t cnt = (n - r0 < kSeqRows ? n - r0 : kSeqRows) * 3;
-        double *d = st.v[k & 1];
-        const double *src = x + 3 * r0;
-        for (int64_t e = tid - 256; e < cnt; e += kT - 256) d[e] = src[e];
-    };
-    const int c = wave >= 1 && wave <= 3 ? wave - 1 : 0;
+    const double sum = block_seq_chain(x, n, st, [](double a, double v) { return dadd(a, v); });
+    if (tid < 3) sh.mean[tid] = ddiv(sum, (double)n);
+    __syncthreads();
+    const double mw = sh.mean[wave % 3];  // the mean of this wave's chain column
     double a = 0.0;
     int forced = 0;
-    stage(0);
+    block_staged_rows<3>(x, n, st, [&](const double *chunk, int rows) {
+        sum_chain_rows(chunk + wave, rows, SqDev{mw}, a, forced);
+    });
+    if (wave < 3 && lane == 0) s.chain[wave] = a;
     __syncthreads();
-    for (int64_t k = 0; k < nch; ++k) {
-        stage(k + 1);
-        const int64_t r0 = k * kSeqRows;
-        const int rows = (int)(n - r0 < kSeqRows ? n - r0 : kSeqRows);
-        if (wave == 0) {
-            if (tid < 3) seq_chain_rows(st.v[k & 1] + tid, rows, tid, step, a0, a1);
-        } else if (wave <= 3) {
-            sum_chain_rows(st.v[k & 1] + c, rows, c, 0, inc, a, forced);
-        }
-        __syncthreads();
-    }
-    if (wave >= 1 && wave <= 3 && lane == 0) s.chain[c] = a;
+    if (tid < 3) sh.std[tid] = __dsqrt_rn(ddiv(s.chain[tid], (double)n));
     __syncthreads();
 }
 
@@ -470,90 +445,31 @@ __device__ __forceinline__ double unordkey(uint64_t k)
     return __longlong_as_double((long long)u);
 }
 
-// ------------------------------------------------------------------ preprocess
-// LIDAR_PRE_DIAG builds (tools/micro/pre_phases.py only): shader-clock stamps of the sections
-// A..I into the frame's scalars 48..57 (cycles since the kernel start)
-#ifdef LIDAR_PRE_DIAG
-#define PRE_STAMP(k)                                                                   \
-    do {                                                                               \
-        __syncthreads();                                                               \
-        if (threadIdx.x == 0) S[48 + (k)] = (double)(clock64() - pre_t0);              \
-    } while (0)
-#else
-#define PRE_STAMP(k) \
-    do {             \
-    } while (0)
-#endif
-__global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict__ xyz_in, int64_t n_in,
-                                                        uint8_t *__restrict__ mask_in,
-                                                        double *__restrict__ colors_in,
-                                                        double *__restrict__ normals_in,
-                                                        double *__restrict__ comp_in,
-                                                        double *__restrict__ sc_in,
-                                                        int32_t *__restrict__ ng_pos_in,
-                                                        double *__restrict__ S_in, FrameMap fm,
-                                                        double fixed_eps)
+// ------------------------------------------------------------------ preprocess: the phases, in kernel order
+// A: the z range over ALL points that the height colours normalise by (data_processing.py:143-147)
+__device__ __forceinline__ void colour_range(BlockScratch &s, const double *xyz, int64_t n, double &zmin, double &denom)
 {
-    __shared__ BlockScratch s;
-    __shared__ SeqStage st;
-    const int tid = threadIdx.x;
-    const int64_t n = fm.n(n_in);
-    const double *xyz = fm.rows(xyz_in, 3);
-    uint8_t *mask = fm.rows(mask_in, 1);
-    double *colors = fm.rows(colors_in, 3), *normals = fm.rows(normals_in, 3), *comp = fm.rows(comp_in, 3);
-    double *sc = fm.ws(sc_in);
-    int32_t *ng_pos = fm.ws(ng_pos_in);
-    double *S = fm.scal(S_in);
-#ifdef LIDAR_PRE_DIAG
-    const long long pre_t0 = clock64();
-#endif
-    if (n == 0) {  // an empty frame of a batch: the reference raises ValueError (status 2)
-        if (tid == 0) S[S_STATUS] = 2.0;
-        return;
-    }
-
-    PRE_STAMP(0);
-    // ---- A: colours over ALL points (data_processing.py:143-147)
     double lo = INFINITY, hi = -INFINITY;
-    for (int64_t i = tid; i < n; i += kT) {
+    for (int64_t i = threadIdx.x; i < n; i += kT) {
         const double z = xyz[3 * i + 2];
         lo = fmin(lo, z);
         hi = fmax(hi, z);
     }
-    const double zmin = block_min(s, lo), zmax = block_max(s, hi);
-    const double denom = dadd(dsub(zmax, zmin), 1e-10);
+    zmin = block_min(s, lo);
+    const double zmax = block_max(s, hi);
+    denom = dadd(dsub(zmax, zmin), 1e-10);
+}
 
-    PRE_STAMP(1);
-    // ---- B: mean / std with numpy's sequential axis-0 sums (:151-152)
-    {
-        double sum = 0.0, unused = 0.0;
-        block_seq_chain(xyz, n, st, [](int, double v, double &a, double &) { a = dadd(a, v); }, sum, unused);
-        if (tid < 3) s.bc[tid] = ddiv(sum, (double)n);
-        __syncthreads();
-        const double mw = s.bc[(tid >> 6) % 3];  // the mean of this wave's chain column
-        block_sum_chain<1>(xyz, n, st, s, [mw](int, int, double v) {
-            const double d = dsub(v, mw);
-            return dmul(d, d);
-        });
-        if (tid < 3) s.bc[3 + tid] = __dsqrt_rn(ddiv(s.chain[tid], (double)n));
-    }
-    __syncthreads();
-    double mean[3], thr[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        mean[c] = s.bc[c];
-        thr[c] = dmul(3.0, s.bc[3 + c]);
-    }
-    if (tid < 3) {
-        S[S_MEAN + tid] = mean[tid];
-        S[S_STD + tid] = s.bc[3 + tid];
-    }
-
-    PRE_STAMP(2);
-    // ---- C: strict 3-sigma mask, order-preserving compaction (:155-157)
+// C: strict 3-sigma mask, order-preserving compaction of the inliers with their colours and normals
+// (:155-161); returns the inlier count
+__device__ __forceinline__ int64_t compact_inliers(BlockScratch &s, const double *xyz, int64_t n,
+                                                   const double (&mean)[3], const double (&thr)[3], double zmin,
+                                                   double denom, uint8_t *mask, double *comp, double *colors,
+                                                   double *normals)
+{
     int64_t nin = 0;
     for (int64_t b0 = 0; b0 < n; b0 += kT) {
-        const int64_t i = b0 + tid;
+        const int64_t i = b0 + threadIdx.x;
         bool f = false;
         double p[3] = {0, 0, 0};
         if (i < n) {
@@ -582,17 +498,15 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         }
         nin += tot;
     }
-    if (tid == 0) {
-        S[S_NIN] = (double)nin;
-        S[S_STATUS] = nin == 0 ? 1.0 : 0.0;
-        S[S_N] = (double)n;
-    }
-    if (nin == 0) return;  // reference: IndexError from np.percentile on an empty array
-    __threadfence_block();
-    __syncthreads();
+    return nin;
+}
 
-    PRE_STAMP(3);
-    // ---- D: z threshold = np.percentile(z, 30) 'linear' (:164)
+// D: z threshold = np.percentile(z, 30) 'linear' (:164) over the z column of the nin compacted points: a radix
+// select of the two order statistics, then numpy's _lerp
+__device__ __forceinline__ double select_z_threshold(BlockScratch &s, SeqStage &st, PreShared &sh, const double *comp,
+                                                     int64_t nin)
+{
+    const int tid = threadIdx.x, wave = tid >> 6;
     const double q = ddiv(30.0, 100.0);
     const double v = dmul((double)(nin - 1), q);
     const double prev = floor(v);
@@ -603,60 +517,58 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         klo = (int64_t)prev;
         khi = klo + 1;
     }
-    double za, zb;
-    {
-        // z column of the compacted points, strided view
-        // (select reads comp[3*i+2] through a small lambda-free loop)
-        uint64_t pre[2] = {0, 0};
-        int64_t kk[2] = {klo, khi};
-        // per-wave histograms (16 waves x 2 targets x 256 bins) in the chain staging memory, idle
-        // here: the early digits of a coordinate column share a few values, and one shared
-        // histogram serialised every wave's atomics on them
-        unsigned *wh = reinterpret_cast<unsigned *>(&st.v[0][0]);
-        static_assert(sizeof(SeqStage) >= kW * 2 * 256 * sizeof(unsigned), "per-wave histograms");
-        const int wave = tid >> 6;
-        for (int pass = 0; pass < 8; ++pass) {
-            const int shift = 56 - 8 * pass;
-            for (int i = tid; i < kW * 2 * 256; i += kT) wh[i] = 0;
-            __syncthreads();
-            unsigned *mine = wh + wave * 2 * 256;
-            for (int64_t i = tid; i < nin; i += kT) {
-                const uint64_t key = ordkey(comp[3 * i + 2]);
-                const uint64_t hk = pass == 0 ? 0 : key >> (shift + 8);
-                const unsigned dig = (unsigned)(key >> shift) & 255u;
-                if (hk == pre[0]) atomicAdd(&mine[dig], 1u);
-                if (hk == pre[1]) atomicAdd(&mine[256 + dig], 1u);
-            }
-            __syncthreads();
-            // thread r * 256 + d holds bin d of target r (waves 4r .. 4r + 3) and its running count: the
-            // bins of one target sum to at most nin < 2^31, so the counts fit 32 bits.  Selected: the
-            // first bin whose running count passes kk[r] (kk[r] is below the target's total: exactly one)
-            const int r = (tid >> 8) & 1;
-            unsigned h = 0;
-            if (tid < 512)
-                for (int w = 0; w < kW; ++w) h += wh[w * 512 + tid];
-            const int64_t cum = block_excl_scan_u32(h, s.i, wave & ~3), kr = r ? kk[1] : kk[0];
-            if (tid < 512 && cum <= kr && kr < cum + h) {
-                s.d[4 + r][0] = __longlong_as_double((long long)(((r ? pre[1] : pre[0]) << 8) | (uint64_t)(tid & 255)));
-                s.d[4 + r][1] = __longlong_as_double((long long)(kr - cum));
-            }
-            __syncthreads();
-            for (int r = 0; r < 2; ++r) {
-                pre[r] = (uint64_t)__double_as_longlong(s.d[4 + r][0]);
-                kk[r] = (int64_t)__double_as_longlong(s.d[4 + r][1]);
-            }
-            __syncthreads();
+    uint64_t pre[2] = {0, 0};
+    int64_t kk[2] = {klo, khi};
+    // per-wave histograms (16 waves x 2 targets x 256 bins) in the chain staging memory, idle
+    // here: the early digits of a coordinate column share a few values, and one shared
+    // histogram serialised every wave's atomics on them
+    unsigned *wh = reinterpret_cast<unsigned *>(&st.v[0][0]);
+    static_assert(sizeof(SeqStage) >= kW * 2 * 256 * sizeof(unsigned), "per-wave histograms");
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        for (int i = tid; i < kW * 2 * 256; i += kT) wh[i] = 0;
+        __syncthreads();
+        unsigned *mine = wh + wave * 2 * 256;
+        for (int64_t i = tid; i < nin; i += kT) {
+            const uint64_t key = ordkey(comp[3 * i + 2]);
+            const uint64_t hk = pass == 0 ? 0 : key >> (shift + 8);
+            const unsigned dig = (unsigned)(key >> shift) & 255u;
+            if (hk == pre[0]) atomicAdd(&mine[dig], 1u);
+            if (hk == pre[1]) atomicAdd(&mine[256 + dig], 1u);
         }
-        za = unordkey(pre[0]);
-        zb = unordkey(pre[1]);
+        __syncthreads();
+        // thread r * 256 + d holds bin d of target r (waves 4r .. 4r + 3) and its running count: the
+        // bins of one target sum to at most nin < 2^31, so the counts fit 32 bits.  Selected: the
+        // first bin whose running count passes kk[r] (kk[r] is below the target's total: exactly one)
+        const int r = (tid >> 8) & 1;
+        unsigned h = 0;
+        if (tid < 512)
+            for (int w = 0; w < kW; ++w) h += wh[w * 512 + tid];
+        const int64_t cum = block_excl_scan_u32(h, s.i, wave & ~3), kr = r ? kk[1] : kk[0];
+        if (tid < 512 && cum <= kr && kr < cum + h) {
+            sh.sel_prefix[r] = ((r ? pre[1] : pre[0]) << 8) | (uint64_t)(tid & 255);
+            sh.sel_rank[r] = kr - cum;
+        }
+        __syncthreads();
+        for (int r = 0; r < 2; ++r) {
+            pre[r] = sh.sel_prefix[r];
+            kk[r] = sh.sel_rank[r];
+        }
+        __syncthreads();
     }
+    const double za = unordkey(pre[0]), zb = unordkey(pre[1]);
     const double t = dsub(v, prev);
     const double diff = dsub(zb, za);
     double zt = dadd(za, dmul(diff, t));
     if (t >= 0.5) zt = dsub(zb, dmul(diff, dsub(1.0, t)));
+    return zt;
+}
 
-    PRE_STAMP(4);
-    // ---- E: ground count and plane (:165-183)
+// E: ground count, dimensions and plane of the nin compacted points (:165-183), into the frame's scalars
+__device__ __forceinline__ void ground_plane(BlockScratch &s, SeqStage &st, const double *comp, int64_t nin, double zt,
+                                             double *S)
+{
+    const int tid = threadIdx.x;
     double cnt = 0, sx = 0, sy = 0, sz = 0, imin[3] = {INFINITY, INFINITY, INFINITY},
            imax[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int64_t i = tid; i < nin; i += kT) {
@@ -679,13 +591,12 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         dmin[c] = block_min(s, imin[c]);
         dmax[c] = block_max(s, imax[c]);
     }
-    const double ng = block_sum(s, cnt, 0);
+    const double ng = block_sum<0>(s, cnt);
     const int64_t nground = (int64_t)ng;
     double plane[4] = {0.0, 0.0, 1.0, -dmin[2]};
     double pkind = 1.0;
     if (nground > 10) {
-        const double mx = block_sum(s, sx, 1) / ng, my = block_sum(s, sy, 2) / ng,
-                     mz = block_sum(s, sz, 3) / ng;
+        const double mx = block_sum<1>(s, sx) / ng, my = block_sum<2>(s, sy) / ng, mz = block_sum<3>(s, sz) / ng;
         // TSQR of the centred, power-of-two-scaled rows (see plane_solve): |w| < 1 per entry
         int exy = 0, ezz = 0;
         const double extxy = fmax(dmax[0] - dmin[0], dmax[1] - dmin[1]), extz = dmax[2] - dmin[2];
@@ -742,12 +653,16 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         for (int c = 0; c < 4; ++c) S[S_PLANE + c] = plane[c];
         S[S_PLANE_KIND] = pkind;
     }
+}
 
-    PRE_STAMP(5);
-    // ---- F: non-ground compaction (:186)
+// F: order-preserving compaction of the non-ground points (:186) into sc, their inlier indices into ng_pos;
+// returns their count
+__device__ __forceinline__ int64_t compact_non_ground(BlockScratch &s, const double *comp, int64_t nin, double zt,
+                                                      double *sc, int32_t *ng_pos)
+{
     int64_t nng = 0;
     for (int64_t b0 = 0; b0 < nin; b0 += kT) {
-        const int64_t i = b0 + tid;
+        const int64_t i = b0 + threadIdx.x;
         const bool f = i < nin && !(comp[3 * i + 2] <= zt);
         int tot;
         const int pos = block_flag_scan(s, f, &tot);
@@ -757,6 +672,153 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         }
         nng += tot;
     }
+    return nng;
+}
+
+// G: sh.smean, sh.sscale = the StandardScaler fit (sklearn _incremental_mean_and_var, zero prior) (:190-191).
+// Ends with a barrier.
+__device__ __forceinline__ void scaler_fit(const double *sc, int64_t nng, SeqStage &st, BlockScratch &s, PreShared &sh)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double nn = (double)nng;
+    const double sum = block_seq_chain(sc, nng, st, [](double a, double v) { return dadd(a, v); });
+    if (tid < 3) sh.smean[tid] = ddiv(sum, nn);
+    __syncthreads();
+    // the second pass, both kinds of chain at once over the same staged rows (one pass instead of two, or
+    // instead of a step carrying both): the sum of deviations stays sequential (lanes 0..2 of wave 0), the sum
+    // of their squares is emulated beside it (waves 1..3, column = wave - 1); waves 4..15 stage
+    const double T = tid < 3 ? sh.smean[tid] : 0.0;
+    const int cw = (wave + 2) % 3;  // waves 1..3: column wave - 1
+    const double Tw = sh.smean[cw];
+    double corr = 0.0, a = 0.0;
+    int forced = 0;
+    block_staged_rows<4>(sc, nng, st, [&](const double *chunk, int rows) {
+        if (wave > 0) sum_chain_rows(chunk + cw, rows, SqDev{Tw}, a, forced);
+        else if (tid < 3) seq_chain_rows(chunk + tid, rows, [T](double cr, double v) { return dadd(cr, dsub(v, T)); }, corr);
+    });
+    if (wave >= 1 && wave <= 3 && lane == 0) s.chain[cw] = a;
+    __syncthreads();
+    if (tid < 3) {
+        double un = s.chain[tid];
+        un = dsub(un, ddiv(dmul(corr, corr), nn));
+        const double var = ddiv(un, nn);
+        const double e = 2.220446049250313e-16;
+        const double ub = dadd(dmul(dmul(nn, e), var), dmul(dmul(dmul(nn, T), e), dmul(dmul(nn, T), e)));
+        sh.sscale[tid] = var <= ub ? 1.0 : __dsqrt_rn(var);
+    }
+    __syncthreads();
+}
+
+// H: transform (X -= mean_; X /= scale_) in place; the bbox of the scaled cloud into the frame's scalars
+__device__ __forceinline__ void scaler_transform(BlockScratch &s, const PreShared &sh, double *sc, int64_t nng, double *S)
+{
+    double smean[3], sscale[3], slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int c = 0; c < 3; ++c) {
+        smean[c] = sh.smean[c];
+        sscale[c] = sh.sscale[c];
+    }
+    for (int64_t i = threadIdx.x; i < nng; i += kT)
+        for (int c = 0; c < 3; ++c) {
+            const double y = ddiv(dsub(sc[3 * i + c], smean[c]), sscale[c]);
+            sc[3 * i + c] = y;
+            slo[c] = fmin(slo[c], y);
+            shi[c] = fmax(shi[c], y);
+        }
+    for (int c = 0; c < 3; ++c) {
+        const double lo = block_min(s, slo[c]), hi = block_max(s, shi[c]);
+        if (threadIdx.x == 0) {
+            S[S_SLO + c] = lo;
+            S[S_SHI + c] = hi;
+        }
+    }
+}
+
+// I: eps = max(0.2, min(0.5, mean(std(scaled, axis=0)) * 0.5)) (:194-195)
+__device__ __forceinline__ double eps_heuristic(const double *sc, int64_t nng, SeqStage &st, BlockScratch &s,
+                                                PreShared &sh)
+{
+    col_moments(sc, nng, st, s, sh);
+    const double avg = dmul(ddiv(dadd(dadd(dadd(0.0, sh.std[0]), sh.std[1]), sh.std[2]), 3.0), 0.5);
+    const double mn = avg < 0.5 ? avg : 0.5;
+    return 0.2 >= mn ? 0.2 : mn;
+}
+
+// LIDAR_PRE_DIAG builds (tools/micro/pre_phases.py only): shader-clock stamps of the phases
+// A..I into the frame's scalars 48..57 (cycles since the kernel start)
+#ifdef LIDAR_PRE_DIAG
+#define PRE_STAMP(k)                                                                   \
+    do {                                                                               \
+        __syncthreads();                                                               \
+        if (threadIdx.x == 0) S[48 + (k)] = (double)(clock64() - pre_t0);              \
+    } while (0)
+#else
+#define PRE_STAMP(k) ((void)0)
+#endif
+__global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict__ xyz_in, int64_t n_in,
+                                                        uint8_t *__restrict__ mask_in,
+                                                        double *__restrict__ colors_in,
+                                                        double *__restrict__ normals_in,
+                                                        double *__restrict__ comp_in,
+                                                        double *__restrict__ sc_in,
+                                                        int32_t *__restrict__ ng_pos_in,
+                                                        double *__restrict__ S_in, FrameMap fm,
+                                                        double fixed_eps)
+{
+    __shared__ BlockScratch s;
+    __shared__ SeqStage st;
+    __shared__ PreShared sh;
+    const int tid = threadIdx.x;
+    const int64_t n = fm.n(n_in);
+    const double *xyz = fm.rows(xyz_in, 3);
+    uint8_t *mask = fm.rows(mask_in, 1);
+    double *colors = fm.rows(colors_in, 3), *normals = fm.rows(normals_in, 3), *comp = fm.rows(comp_in, 3);
+    double *sc = fm.ws(sc_in);
+    int32_t *ng_pos = fm.ws(ng_pos_in);
+    double *S = fm.scal(S_in);
+#ifdef LIDAR_PRE_DIAG
+    const long long pre_t0 = clock64();
+#endif
+    if (n == 0) {  // an empty frame of a batch: the reference raises ValueError (status 2)
+        if (tid == 0) S[S_STATUS] = 2.0;
+        return;
+    }
+
+    PRE_STAMP(0);  // A
+    double zmin, denom;
+    colour_range(s, xyz, n, zmin, denom);
+
+    PRE_STAMP(1);  // B: mean / std with numpy's sequential axis-0 sums (:151-152)
+    col_moments(xyz, n, st, s, sh);
+    double mean[3], thr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mean[c] = sh.mean[c];
+        thr[c] = dmul(3.0, sh.std[c]);
+    }
+    if (tid < 3) {
+        S[S_MEAN + tid] = sh.mean[tid];
+        S[S_STD + tid] = sh.std[tid];
+    }
+
+    PRE_STAMP(2);  // C
+    const int64_t nin = compact_inliers(s, xyz, n, mean, thr, zmin, denom, mask, comp, colors, normals);
+    if (tid == 0) {
+        S[S_NIN] = (double)nin;
+        S[S_STATUS] = nin == 0 ? 1.0 : 0.0;
+        S[S_N] = (double)n;
+    }
+    if (nin == 0) return;  // reference: IndexError from np.percentile on an empty array
+    __threadfence_block();
+    __syncthreads();
+
+    PRE_STAMP(3);  // D
+    const double zt = select_z_threshold(s, st, sh, comp, nin);
+
+    PRE_STAMP(4);  // E
+    ground_plane(s, st, comp, nin, zt, S);
+
+    PRE_STAMP(5);  // F
+    const int64_t nng = compact_non_ground(s, comp, nin, zt, sc, ng_pos);
     if (tid == 0) S[S_NNG] = (double)nng;
     if (nng <= 10) return;  // reference: all non-ground labelled 0, no DBSCAN (:199-200)
     __threadfence_block();
@@ -775,94 +837,27 @@ __global__ __launch_bounds__(kT) void preprocess_kernel(const double *__restrict
         return;
     }
 
-    PRE_STAMP(6);
-    // ---- G: StandardScaler fit (sklearn _incremental_mean_and_var, zero prior) (:190-191)
-    {
-        const double nn = (double)nng;
-        double sum = 0.0, unused = 0.0;
-        block_seq_chain(sc, nng, st, [](int, double v, double &a, double &) { a = dadd(a, v); }, sum, unused);
-        if (tid < 3) s.bc[6 + tid] = ddiv(sum, nn);
-        __syncthreads();
-        const double Tc = tid < 3 ? s.bc[6 + tid] : 0.0;
-        // the second pass: sum of deviations (sequential) and, beside it, the sum of their squares (emulated)
-        const double Tw = s.bc[6 + ((tid >> 6) + 2) % 3];  // waves 1..3: the mean of column wave - 1
-        double corr = 0.0, unused2 = 0.0;
-        block_seq_sum_chain(sc, nng, st, s, [Tc](int, double v, double &cr, double &) { cr = dadd(cr, dsub(v, Tc)); },
-                            corr, unused2, [Tw](int, int, double v) {
-                                const double d = dsub(v, Tw);
-                                return dmul(d, d);
-                            });
-        if (tid < 3) {
-        const double T = Tc;
-        double un = s.chain[tid];
-        un = dsub(un, ddiv(dmul(corr, corr), nn));
-        const double var = ddiv(un, nn);
-        const double e = 2.220446049250313e-16;
-        const double ub = dadd(dmul(dmul(nn, e), var), dmul(dmul(dmul(nn, T), e), dmul(dmul(nn, T), e)));
-        const double scale = var <= ub ? 1.0 : __dsqrt_rn(var);
-        s.bc[6 + tid] = T;
-        s.bc[9 + tid] = scale;
-        }
-    }
-    __syncthreads();
-    double smean[3], sscale[3];
-    for (int c = 0; c < 3; ++c) {
-        smean[c] = s.bc[6 + c];
-        sscale[c] = s.bc[9 + c];
-    }
+    PRE_STAMP(6);  // G
+    scaler_fit(sc, nng, st, s, sh);
     if (tid < 3) {
-        S[S_SMEAN + tid] = smean[tid];
-        S[S_SSCALE + tid] = sscale[tid];
+        S[S_SMEAN + tid] = sh.smean[tid];
+        S[S_SSCALE + tid] = sh.sscale[tid];
     }
-    PRE_STAMP(7);
-    // ---- H: transform (X -= mean_; X /= scale_) and bbox of the scaled cloud
-    double slo[3] = {INFINITY, INFINITY, INFINITY}, shi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int64_t i = tid; i < nng; i += kT)
-        for (int c = 0; c < 3; ++c) {
-            const double y = ddiv(dsub(sc[3 * i + c], smean[c]), sscale[c]);
-            sc[3 * i + c] = y;
-            slo[c] = fmin(slo[c], y);
-            shi[c] = fmax(shi[c], y);
-        }
-    double blo[3], bhi[3];
-    for (int c = 0; c < 3; ++c) {
-        blo[c] = block_min(s, slo[c]);
-        bhi[c] = block_max(s, shi[c]);
-    }
+
+    PRE_STAMP(7);  // H
+    scaler_transform(s, sh, sc, nng, S);
     __threadfence_block();
     __syncthreads();
-    PRE_STAMP(8);
-    // ---- I: eps = max(0.2, min(0.5, mean(std(scaled, axis=0)) * 0.5)) (:194-195)
-    {
-        const double nn = (double)nng;
-        double sum = 0.0, unused = 0.0;
-        block_seq_chain(sc, nng, st, [](int, double v, double &a, double &) { a = dadd(a, v); }, sum, unused);
-        if (tid < 3) s.bc[12 + tid] = ddiv(sum, nn);
-        __syncthreads();
-        const double mw = s.bc[12 + (tid >> 6) % 3];
-        block_sum_chain<1>(sc, nng, st, s, [mw](int, int, double v) {
-            const double d = dsub(v, mw);
-            return dmul(d, d);
-        });
-        if (tid < 3) s.bc[12 + tid] = __dsqrt_rn(ddiv(s.chain[tid], nn));
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double avg = dmul(ddiv(dadd(dadd(dadd(0.0, s.bc[12]), s.bc[13]), s.bc[14]), 3.0), 0.5);
-        const double mn = avg < 0.5 ? avg : 0.5;
-        const double eps = 0.2 >= mn ? 0.2 : mn;
-        S[S_EPS] = eps;
-        for (int c = 0; c < 3; ++c) {
-            S[S_SLO + c] = blo[c];
-            S[S_SHI + c] = bhi[c];
-        }
-    }
+
+    PRE_STAMP(8);  // I
+    const double eps = eps_heuristic(sc, nng, st, s, sh);
+    if (tid == 0) S[S_EPS] = eps;
     PRE_STAMP(9);
 }
 
-// full labels over the inliers: ground -1, non-ground = DBSCAN label (or 0 when <= 10)
-__global__ void scatter_labels_kernel(const double *S_in, const int64_t *ng_labels_in, const int32_t *ng_pos_in,
-                                      int64_t *full_in, FrameMap fm)
+// full labels over the inliers: ground -1, non-ground = DBSCAN label (or 0 when <= 10).  Two launches (a fill
+// and a scatter in one would race across workgroups): first -1 everywhere,
+__global__ void ground_fill_kernel(const double *S_in, int64_t *full_in, FrameMap fm)
 {
     const double *S = fm.scal(S_in);
     int64_t *full = fm.rows(full_in, 1);
@@ -870,10 +865,10 @@ __global__ void scatter_labels_kernel(const double *S_in, const int64_t *ng_labe
     const int64_t nin = (int64_t)S[S_NIN];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nin; i += stride) full[i] = -1;
-    __syncthreads();
 }
-__global__ void scatter_labels2_kernel(const double *S_in, const int64_t *ng_labels_in, const int32_t *ng_pos_in,
-                                       int64_t *full_in, FrameMap fm)
+// then the non-ground points' labels at their inlier indices
+__global__ void cluster_label_scatter_kernel(const double *S_in, const int64_t *ng_labels_in, const int32_t *ng_pos_in,
+                                             int64_t *full_in, FrameMap fm)
 {
     const double *S = fm.scal(S_in);
     const int64_t *ng_labels = fm.ws(ng_labels_in);
@@ -890,7 +885,7 @@ __global__ void scatter_labels2_kernel(const double *S_in, const int64_t *ng_lab
 // offs == nullptr: one frame of n points)
 int run_preprocess(lidar_handle *h, const double *xyz, int64_t n, const int64_t *offs, int frames, uint8_t *mask,
                    double *colors, double *normals, double *compact_xyz, int64_t *labels, double *scalars,
-                   hipStream_t s, double fixed_eps = 0.0)
+                   hipStream_t s, double fixed_eps)
 {
     lidar::Carver cv;
     const uint64_t o_sc = cv.take<double>(3 * n);
@@ -920,8 +915,9 @@ int run_preprocess(lidar_handle *h, const double *xyz, int64_t n, const int64_t 
     if (rc) return rc;
     const unsigned gp = point_blocks(n, frames);
     lidar::Span sp(h, "label_scatter", s);
-    hipLaunchKernelGGL(scatter_labels_kernel, dim3(gp, frames), dim3(256), 0, s, scalars, ng_lab, ng_pos, labels, fm);
-    hipLaunchKernelGGL(scatter_labels2_kernel, dim3(gp, frames), dim3(256), 0, s, scalars, ng_lab, ng_pos, labels, fm);
+    hipLaunchKernelGGL(ground_fill_kernel, dim3(gp, frames), dim3(256), 0, s, scalars, labels, fm);
+    hipLaunchKernelGGL(cluster_label_scatter_kernel, dim3(gp, frames), dim3(256), 0, s, scalars, ng_lab, ng_pos, labels,
+                       fm);
     dbscan_nclust_to_scalars(w, scalars, s, fm, frames);
     LAUNCH_CHECK();
     return LIDAR_OK;
@@ -930,16 +926,30 @@ int run_preprocess(lidar_handle *h, const double *xyz, int64_t n, const int64_t 
 }  // namespace
 
 // ====================================================================== C-ABI
+// the three entry points' argument checks and call.  who: the entry point's name; nname: its name for the point
+// count; offs_optional: offsets may be null (one frame of n points); eps: null for the scaled path
+static int preprocess_entry(const std::string &who, const char *nname, bool offs_optional, lidar_handle *h,
+                            const double *xyz, const int64_t *offsets, int32_t frames, int64_t n, const double *eps,
+                            uint8_t *mask, double *colors, double *normals, double *compact_xyz, int64_t *labels,
+                            double *scalars, void *stream)
+{
+    REQUIRE(h && xyz && (offsets || offs_optional) && mask && colors && normals && compact_xyz && labels && scalars,
+            who + ": null pointer");
+    REQUIRE(frames >= 1 && frames <= 65535 && (offsets || frames == 1),
+            who + ": need 1 <= frames <= 65535" + (offs_optional ? " (offsets for frames > 1)" : ""));
+    REQUIRE(n >= 1 && n < 0x7fffffff, who + ": need 1 <= " + nname + " < 2^31");
+    REQUIRE(!eps || (*eps > 0.0 && *eps < INFINITY), who + ": eps must be finite and > 0");
+    ON_DEVICE(h->device);
+    return run_preprocess(h, xyz, n, offsets, frames, mask, colors, normals, compact_xyz, labels, scalars,
+                          static_cast<hipStream_t>(stream), eps ? *eps : 0.0);
+}
+
 LIDAR_EXPORT int lidar_preprocess_f64(lidar_handle *h, const double *xyz, int64_t n, uint8_t *mask,
                                       double *colors, double *normals, double *compact_xyz,
                                       int64_t *labels, double *scalars, void *stream)
 {
-    REQUIRE(h && xyz && mask && colors && normals && compact_xyz && labels && scalars,
-            "lidar_preprocess_f64: null pointer");
-    REQUIRE(n >= 1 && n < 0x7fffffff, "lidar_preprocess_f64: need 1 <= n < 2^31");
-    ON_DEVICE(h->device);
-    return run_preprocess(h, xyz, n, nullptr, 1, mask, colors, normals, compact_xyz, labels, scalars,
-                          static_cast<hipStream_t>(stream));
+    return preprocess_entry("lidar_preprocess_f64", "n", true, h, xyz, nullptr, 1, n, nullptr, mask, colors, normals,
+                            compact_xyz, labels, scalars, stream);
 }
 
 LIDAR_EXPORT int lidar_preprocess_batch_f64(lidar_handle *h, const double *xyz, const int64_t *offsets,
@@ -947,13 +957,8 @@ LIDAR_EXPORT int lidar_preprocess_batch_f64(lidar_handle *h, const double *xyz, 
                                             double *normals, double *compact_xyz, int64_t *labels,
                                             double *scalars, void *stream)
 {
-    REQUIRE(h && xyz && offsets && mask && colors && normals && compact_xyz && labels && scalars,
-            "lidar_preprocess_batch_f64: null pointer");
-    REQUIRE(frames >= 1 && frames <= 65535, "lidar_preprocess_batch_f64: need 1 <= frames <= 65535");
-    REQUIRE(max_n >= 1 && max_n < 0x7fffffff, "lidar_preprocess_batch_f64: need 1 <= max_n < 2^31");
-    ON_DEVICE(h->device);
-    return run_preprocess(h, xyz, max_n, offsets, frames, mask, colors, normals, compact_xyz, labels, scalars,
-                          static_cast<hipStream_t>(stream));
+    return preprocess_entry("lidar_preprocess_batch_f64", "max_n", false, h, xyz, offsets, frames, max_n, nullptr, mask,
+                            colors, normals, compact_xyz, labels, scalars, stream);
 }
 
 // the variant pipeline's preprocess (app_simplified.py:76-137, app_with_db.py:80-141):
@@ -964,13 +969,6 @@ LIDAR_EXPORT int lidar_preprocess_eps_batch_f64(lidar_handle *h, const double *x
                                                 double *colors, double *normals, double *compact_xyz,
                                                 int64_t *labels, double *scalars, void *stream)
 {
-    REQUIRE(h && xyz && mask && colors && normals && compact_xyz && labels && scalars,
-            "lidar_preprocess_eps_batch_f64: null pointer");
-    REQUIRE(frames >= 1 && frames <= 65535 && (offsets || frames == 1),
-            "lidar_preprocess_eps_batch_f64: need 1 <= frames <= 65535 (offsets for frames > 1)");
-    REQUIRE(max_n >= 1 && max_n < 0x7fffffff, "lidar_preprocess_eps_batch_f64: need 1 <= max_n < 2^31");
-    REQUIRE(eps > 0.0 && eps < INFINITY, "lidar_preprocess_eps_batch_f64: eps must be finite and > 0");
-    ON_DEVICE(h->device);
-    return run_preprocess(h, xyz, max_n, offsets, frames, mask, colors, normals, compact_xyz, labels, scalars,
-                          static_cast<hipStream_t>(stream), eps);
+    return preprocess_entry("lidar_preprocess_eps_batch_f64", "max_n", true, h, xyz, offsets, frames, max_n, &eps, mask,
+                            colors, normals, compact_xyz, labels, scalars, stream);
 }

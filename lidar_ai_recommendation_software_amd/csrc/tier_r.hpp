@@ -78,11 +78,11 @@ __device__ __forceinline__ int64_t arange_bin(double a, double g, int64_t nb, do
 struct BlockScratch {
     double d[6][kW];
     uint32_t i[kW];
-    double bc[16];  // broadcast
-    double chain[6];  // block_sum_chain results: [accumulator * 3 + column]
+    double chain[3];  // preprocess.hip's emulated chains: the result of column c
 };
 
-// workgroup reduction of v with op (fmin or fmax, through row `SLOT` of s.d): every thread gets the result
+// workgroup reduction of v with op (fmin, fmax, or preprocess.hip's dadd; through row `SLOT` of s.d) in a fixed
+// order (the xor butterfly within a wave, then the waves' results in wave order): every thread gets the result
 template <int SLOT, class Op>
 __device__ __forceinline__ double block_reduce(BlockScratch &s, double v, Op op)
 {

@@ -1,4 +1,4 @@
-"""The parallel emulation of a sequential fp64 sum (preprocess.hip block_sum_chain),
+"""The parallel emulation of a sequential fp64 sum (preprocess.hip sum_chain_rows),
 restated in numpy and checked against the plain sequential loop on adversarial inputs.
 
 The kernel itself is checked on the GPU (tests/test_gpu_tier_r.py: the reference's goldens and

@@ -1057,10 +1057,34 @@ def test_preprocess_chain_stress_vs_oracle(cuda, kind):
         with pytest.raises(type(e)):
             dp.preprocess_lidar_data(pts)
         return
-    got = dp.preprocess_lidar_data(pts)
+    _same_preprocess(kind, dp.preprocess_lidar_data(pts), want)
+
+
+def _same_preprocess(name, got, want):
     for k in ("points", "colors", "normals", "clusters"):
         a, b = np.asarray(got[k]), np.asarray(want[k])
-        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{kind}.{k}"
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), f"{name}.{k}"
     for k in ("x_range", "y_range", "z_range"):
         assert [float(v).hex() for v in got["dimensions"][k]] == [float(v).hex() for v in want["dimensions"][k]]
-    check_plane(kind, got["ground_plane"], want["ground_plane"], want["points"])
+    check_plane(name, got["ground_plane"], want["ground_plane"], want["points"])
+
+
+# frame sizes that end a staged chunk of the chains (3 072 rows) exactly, one row short and one row past, after
+# one chunk and after two: over all points (the mean / std of the 3-sigma filter; every point of these frames
+# is an inlier) and over the non-ground points (the scaler's fit and the eps heuristic).  n -> the non-ground
+# count it is chosen for (None: the seam is n itself)
+CHUNK_SEAMS = {3071: None, 3072: None, 3073: None, 6144: None, 6145: None,
+               4389: 3072, 4390: 3073, 8777: 6144, 8779: 6145}
+
+
+@pytest.mark.parametrize("n", sorted(CHUNK_SEAMS))
+def test_preprocess_chunk_seams_vs_oracle(cuda, n):
+    """preprocess_lidar_data == the oracle byte for byte (the plane by check_plane) on uniform frames whose point
+    count, or non-ground count, sits on a seam of the chains' staged chunks: a full last chunk, a 1-row last
+    chunk, a last chunk one row short. No golden frame does."""
+    pts = uniform_frame(n, 0)
+    want = tier_r.preprocess_lidar_data(pts.copy())
+    assert len(want["points"]) == n, "every point is a 3-sigma inlier"
+    if CHUNK_SEAMS[n] is not None:
+        assert int((np.asarray(want["clusters"]) != -1).sum()) == CHUNK_SEAMS[n], "non-ground count off the seam"
+    _same_preprocess(f"uniform_{n}", dp.preprocess_lidar_data(pts), want)

@@ -53,8 +53,8 @@ DBSCAN and radius count (dbscan.hip carve_dbscan, run_dbscan_on)
   * ``partial``: scan_partial_kernel writes one word per block before scan_top_kernel / scan_final_kernel read them.
 Preprocess chain (preprocess.hip run_preprocess, one slice of ``wss`` bytes per frame)
   * ``sc`` double[3n], ``ng_pos`` int32[n]: preprocess_kernel writes the nng scaled non-ground rows before DBSCAN
-    (as its ``x``) and scatter_labels2_kernel read [0, nng).
-  * ``ng_lab`` int64[n]: dbscan_labels_kernel writes [0, nng) of an active frame; scatter_labels2_kernel reads it
+    (as its ``x``) and cluster_label_scatter_kernel read [0, nng).
+  * ``ng_lab`` int64[n]: dbscan_labels_kernel writes [0, nng) of an active frame; cluster_label_scatter_kernel reads it
     only when nng > 10, which is when the frame is active.
   * the DBSCAN sub-buffers as above, with ``P`` written by dbscan_params_from_preprocess from the frame's scalars.
     That kernel left P[P_NCLUST] to dbscan_labels_kernel, which skips an inactive frame (failed, or <= 10

@@ -1,4 +1,5 @@
-// The preprocess kernel's sequential-chain structure in isolation (preprocess.hip block_seq_chain):
+// The preprocess kernel's sequential-chain structure in isolation (preprocess.hip block_seq_chain,
+// there one caller of block_staged_rows):
 // a 1024-thread workgroup, waves 1..15 stage 1024-row (n, 3) fp64 chunks into LDS (double
 // buffered), lanes 0..2 of wave 0 run the dependent adds.  Variants of the consumer loop:
 //   0: batches of 16 reads, then 16 dependent adds (the kernel's form)
