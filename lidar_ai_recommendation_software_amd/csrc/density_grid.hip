@@ -19,7 +19,7 @@ using namespace lidar::tier_r;
 // (wave w owns points [64(w-1), 64w) of every chunk) into LDS contiguously in index order
 // (double-buffered rows, triple-buffered per-wave counts), and lanes 0 / 1 of wave 0 run the
 // x / y chains over the chunk's members in one run, as np.mean of the member rows does
-// (sequential axis-0 sums starting from the first row).  Per chunk: the staging waves place
+// (sequential axis-0 sums starting from the identity +0.0).  Per chunk: the staging waves place
 // chunk k+1 (its counts were published a phase earlier) and count chunk k+2 while wave 0 adds
 // chunk k; one barrier per chunk.
 __global__ __launch_bounds__(kT) void people_kernel(const double *xyz_in, const int64_t *labels_in, int64_t n_in,
@@ -72,11 +72,7 @@ __global__ __launch_bounds__(kT) void people_kernel(const double *xyz_in, const 
                 int tot = 0;
                 for (int w = 1; w < kW; ++w) tot += wcnt[k % 3][w];
                 const double *b = mem[k & 1] + tid;
-                int j = 0;
-                if (cnt == 0 && tot > 0) {  // np.add.reduce starts from the first row
-                    acc = b[0];
-                    j = 1;
-                }
+                int j = 0;  // acc starts at +0.0, np.add.reduce's identity: members that are all -0.0 sum to +0.0
                 for (; j + 16 <= tot; j += 16) {  // reads first, then the dependent adds
                     double v[16];
 #pragma unroll
