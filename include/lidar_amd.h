@@ -625,6 +625,56 @@ int lidar_track_history_f64(lidar_handle *h, const double *people, const int64_t
                             int32_t nzones, int32_t *age, int32_t *hits, double *path, double *origin,
                             int32_t *stay, int64_t *dwell, void *stream);
 
+/* Crowding (csrc/track_crowding.hip; DESIGN.md §3 "Crowding", §4.15): per tracked person the number of people
+ * within a radius, the nearest one and the distance to it, the local density, and the variance of the velocities
+ * around it with their product, the crowd pressure; per frame and per venue cell the counts above two limits and
+ * the peaks.  Asynchronous like its siblings: every pointer a device pointer, no host synchronisation, nothing
+ * read back, no host-staged parameter block, no scratch; no output depends on an earlier call.  All arithmetic
+ * fp64, one rounding per operation, the square root and the divisions correctly rounded.
+ *
+ * lidar_track_crowding_f64: people, k, frames, cap and K_t as lidar_track_people_f64; prev (frames, cap) int32 and
+ * velocity (frames, cap, 2) as lidar_track_people_f64 / lidar_track_stream_f64 leave them.  Only the frames
+ * t >= first are evaluated (with a carry in front: first = carry, as lidar_track_events_f64), each on its own.
+ * valid(j): j < K_t and both coordinates finite.  moving(j): valid(j) and prev[t][j] >= 0 and both velocity
+ * components finite.  d(i, j) = (dx*dx) + (dy*dy), dx = P[i].x - P[j].x, dy = P[i].y - P[j].y.  near(i, j): i != j,
+ * valid(i) and d <= R*R, R = radius (inclusive; R*R one product); d(i, j) and d(j, i) have the same bits, so near
+ * is symmetric.
+ * Per row, arrays (frames - first, cap) indexed by t - first, every element written; for a valid row j:
+ *   neighbours int32 = #{i : near(i, j)};
+ *   nearest int32 = the valid i != j with finite d and the smallest (d, i), lexicographic, over the whole frame
+ *     (not only within R); -1 without one;
+ *   spacing fp64 = sqrt(d(nearest, j)); +inf where nearest == -1;
+ *   density fp64 = (double)(neighbours + 1) / ((pi * R) * R), pi = M_PI, the two products in that order;
+ *   movers int32 = m = |M_j|, M_j = {i : moving(i) and (i == j or near(i, j))};
+ *   variance fp64: sx, sy, sq = the sums of vx, vy and (vx*vx) + (vy*vy) over M_j, each added sequentially in
+ *     ascending i from +0.0 (row j in its own place); m >= 2: mx = sx / m, my = sy / m,
+ *     var = (sq / m) - ((mx*mx) + (my*my)), a non-NaN var that is not > 0.0 becomes +0.0; m < 2: +0.0;
+ *   pressure fp64 = density * variance.
+ * A row j < K_t that is not valid gets neighbours 0, nearest -1, spacing +inf, movers 0 and 0.0 for the three
+ * other doubles and is counted nowhere below; a row at or past K_t the same with neighbours -1.  A NaN's payload
+ * and sign are free.
+ * crowded (frames - first, 2) int32: the valid rows with density >= density_limit, with pressure >=
+ * pressure_limit.  peaks (frames - first, 3) fp64: the largest density and the largest pressure over the valid
+ * rows (from +0.0, replaced under >: a NaN never wins), the smallest spacing (from +inf, replaced under <).
+ * Cells, with nx > 0 (nx == 0: no cell output, the grid arguments and cell pointers unused): the grid
+ * (x0, y0, grid, nx, ny) is lidar_flow_cells_f64's, a row outside it dropped.  cell_peak (nx, ny, 2) fp64: the
+ * largest density and pressure, cell_crowded (nx, ny) int32: the number with density >= density_limit, of the
+ * valid rows of the frames >= first, each binned by its own position.  accumulate = 0 starts from 0; 1 goes on
+ * from the stored values (non-negative, not NaN: what a call leaves), so a stream's calls give the bits of one
+ * call over the whole sequence.  Every result is the same under every schedule.
+ *
+ * LIDAR_EINVAL: a null handle, people, k, prev, velocity or per-row / per-frame output; frames < 0 or > 65535,
+ * cap < 1, frames * cap >= 2^31; first outside 0 .. frames; radius not positive and finite; a limit that is NaN
+ * or negative (+inf: never); accumulate not 0 or 1; nx < 0; with nx > 0 the grid conditions of
+ * lidar_flow_cells_f64 or a null cell_peak / cell_crowded.  frames == first returns LIDAR_OK and writes nothing. */
+int lidar_track_crowding_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                             const double *velocity, int64_t frames, int64_t cap, int64_t first, double radius,
+                             double density_limit, double pressure_limit, double x0, double y0, double grid,
+                             int64_t nx, int64_t ny, int32_t accumulate, int32_t *neighbours, int32_t *nearest,
+                             double *spacing, double *density, int32_t *movers, double *variance, double *pressure,
+                             int32_t *crowded, double *peaks, double *cell_peak, int32_t *cell_crowded,
+                             void *stream);
+
 /* the density grid + statistics + hotspots of every frame with K_f > 0.  jobs: device
  * double[8 * frames] rows (xa = x_min - 2g, ya = y_min - 2g, g, nx, ny (lidar_grid_dims),
  * output offset, scratch offset, 0); out at a frame's offset: grid_x (nx) | grid_y (ny) |

@@ -129,8 +129,35 @@ class CrowdFlowModel:
                         "zone_dwell_mean_s": mean})
         return out
 
+    RISK_LEVELS = ("Low", "Moderate", "High", "Critical")  # calculate_risk_level's classes, risk_levels' columns
+
+    @classmethod
+    def _crowding_keys(cls, K, host, crowded_total, peak_total):
+        """The crowding keys of analyze_sequence / analyze_stream from host copies: in `host`, under their names,
+        people and track_crowding's nine per-row and per-frame arrays over the frames K, and the two cell arrays of
+        the venue grid; crowded_total (2,) and peak_total (3,) of the whole stream."""
+        from .crowd_density_model import CrowdDensityModel
+
+        rows = range(len(K))
+        level = CrowdDensityModel().calculate_risk_level
+        risk = np.zeros((len(K), len(cls.RISK_LEVELS)), dtype=np.int64)
+        for t in rows:
+            valid = np.isfinite(host["people"][t, :K[t]]).all(axis=1)
+            for d in host["density"][t, :K[t]][valid]:
+                risk[t, cls.RISK_LEVELS.index(level(d))] += 1
+        out = {key: [host[name][t, :K[t]] for t in rows] for key, name in (
+            ("neighbours", "neighbours"), ("nearest", "nearest"), ("spacings", "spacing"),
+            ("local_density", "density"), ("velocity_variance", "variance"), ("pressure", "pressure"))}
+        out.update({"crowded_series": host["crowded"], "peak_series": host["peaks"],
+                    "crowded_total": crowded_total.astype(np.int64), "peak_density": float(peak_total[0]),
+                    "peak_pressure": float(peak_total[1]), "min_spacing": float(peak_total[2]),
+                    "crowd_peak_cells": {"density": host["cell_peak"][:, :, 0], "pressure": host["cell_peak"][:, :, 1]},
+                    "crowded_cells": host["cell_crowded"], "risk_levels": risk})
+        return out
+
     def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
-                         min_observations=1, max_gap=0, gates=None, zones=None, history=False):
+                         min_observations=1, max_gap=0, gates=None, zones=None, history=False, crowding=None,
+                         density_limit=4.0, pressure_limit=0.02):
         """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
 
         people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
@@ -168,7 +195,21 @@ class CrowdFlowModel:
         0 .. tracks - 1, frames counted from 0.  With zones also zone_stays, per frame (K_t, Z) int32 (frames since
         the row's present stay in the zone began, -1 outside); zone_dwell_count, zone_dwell_frames and
         zone_dwell_max (Z,) int64 (the completed stays, their summed and largest length in frames) and
-        zone_dwell_mean_s (Z,) float64 = dt * frames / count, NaN without a completed stay."""
+        zone_dwell_mean_s (Z,) float64 = dt * frames / count, NaN without a completed stay.
+
+        crowding=R, a radius in metres, adds how tightly packed every person is and how coherently the people around
+        it move (``people_tracking.track_crowding``, DESIGN.md §3 "Crowding"), in the same read-back: neighbours and
+        nearest per frame (K_t,) int32 (the people within R, the row of the closest person of the frame or -1);
+        spacings, local_density, velocity_variance and pressure per frame (K_t,) float64 (metres to the nearest
+        person, (neighbours + 1) / (pi R^2) people per m^2, the variance of the measured velocities of the person and
+        its neighbours, and their product, the crowd pressure of Helbing et al. 2007); crowded_series (T, 2) int32
+        (the people at or above density_limit, at or above pressure_limit) and peak_series (T, 3) float64 (largest
+        density, largest pressure, smallest spacing) per frame; crowded_total (2,) int64, peak_density,
+        peak_pressure and min_spacing over the sequence; crowd_peak_cells {"density", "pressure"} (nx, ny) float64 and
+        crowded_cells (nx, ny) int32 on the venue grid; risk_levels (T, 4) int64, the people of each frame in
+        ``CrowdDensityModel.calculate_risk_level``'s classes Low / Moderate / High / Critical of their local
+        density.  density_limit 4.0 people per m^2 is that function's "Critical" edge and pressure_limit 0.02 1/s^2
+        the turbulence level Helbing et al. report: defaults to override per venue, not measurements."""
         import torch
         from . import people_tracking as pt
 
@@ -188,6 +229,9 @@ class CrowdFlowModel:
         max_gap = pt._integer(what, "max_gap", max_gap, pt.MAX_GAP)
         gates = None if gates is None else pt.check_gates(gates)
         zones = None if zones is None else pt.check_zones(zones)
+        if crowding is not None:
+            crowding = pt._crowding_options(what, {"radius": crowding, "density_limit": density_limit,
+                                                   "pressure_limit": pressure_limit})
         if isinstance(people, torch.Tensor):
             if k is None:
                 raise ValueError("analyze_sequence: a people tensor needs k")
@@ -220,6 +264,10 @@ class CrowdFlowModel:
             named["people"] = people
             named.update(zip([name for name, _, _ in pt.HISTORY] + ["stay", "dwell"],
                              pt.track_history(people, k, prev, gap, tables[1])))
+        if crowding is not None:
+            named["people"] = people
+            named.update(zip(pt.CROWDING, pt.track_crowding(people, k, prev, velocity, crowding[0], *crowding[1],
+                                                            x_range, y_range, grid_size)))
         host = _read_back(named, people.device)  # the one read-back
         K = np.minimum(np.maximum(host["k"], 0), people.shape[1])
         extras = self._track_keys(K, host, int(np.sum(host["prev"] >= 0)))
@@ -231,6 +279,10 @@ class CrowdFlowModel:
             total = None if dwell is None else np.concatenate(
                 [dwell[:, :, :2].sum(axis=0), dwell[:, :, 2].max(axis=0, initial=0)[:, None]], axis=1)
             extras.update(self._history_keys(K, np.arange(len(K)), host, total, dt))
+        if crowding is not None:
+            peaks = host["peaks"]
+            extras.update(self._crowding_keys(K, host, host["crowded"].sum(axis=0), np.array(
+                [peaks[:, 0].max(initial=0.0), peaks[:, 1].max(initial=0.0), peaks[:, 2].min(initial=np.inf)])))
         return self._measured_flow(host["count"], host["vsum"], x_range, y_range, grid_size, min_observations, extras)
 
     def analyze_stream(self, tracker, min_observations=1):
@@ -243,7 +295,9 @@ class CrowdFlowModel:
         gate_series, zone_occupancy, gate_events and zone_membership cover the held frames.  A tracker built with
         history=True adds ``analyze_sequence``'s history keys, in the same read-back: the per-frame lists cover the
         held frames, track_table the tracks present in them (frames counted from the first pushed frame), and the
-        zone_dwell keys total the whole stream."""
+        zone_dwell keys total the whole stream.  A tracker built with crowding adds ``analyze_sequence``'s crowding
+        keys, in the same read-back: the per-frame lists, crowded_series, peak_series and risk_levels cover the held
+        frames; crowded_total, peak_density, peak_pressure, min_spacing and the two cell maps the whole stream."""
         import torch
 
         if int(min_observations) != min_observations or min_observations < 1:
@@ -256,13 +310,19 @@ class CrowdFlowModel:
                         zone_total=np.zeros((tracker.Z, 2), dtype=np.int64))
             if tracker.history and tracker.Z:
                 host["dwell_total"] = np.zeros((tracker.Z, 3), dtype=np.int64)
+            if tracker.crowding:
+                host.update(crowded_total=np.zeros(2, dtype=np.int64), peak_total=np.array([0.0, 0.0, np.inf]),
+                            cell_peak=np.zeros(tracker.grid[2:] + (2,)),
+                            cell_crowded=np.zeros(tracker.grid[2:], dtype=np.int32))
         else:
             held = tracker.held()
-            for name in ("prev", "succ") + (() if tracker.history else ("people",)):
-                del held[name]  # no key needs them (the positions: only the history keys)
+            for name in ("prev", "succ") + (() if tracker.history or tracker.crowding else ("people",)):
+                del held[name]  # no key needs them (the positions: only the history and crowding keys)
             host = _read_back({**held, "ntracks": tracker.ntracks, "matched": tracker.matched, "count": tracker.count,
                                "vsum": tracker.vsum, "gate_total": tracker.gate_total,
-                               "zone_total": tracker.zone_total, "dwell_total": tracker.dwell_total},
+                               "zone_total": tracker.zone_total, "dwell_total": tracker.dwell_total,
+                               "crowded_total": tracker.crowded_total, "peak_total": tracker.peak_total,
+                               "cell_peak": tracker.cell_peak, "cell_crowded": tracker.cell_crowded},
                               tracker.ntracks.device)  # the one read-back
         K = np.minimum(np.maximum(host["k"], 0), tracker.cap or 1)
         extras = self._track_keys(K, host, int(host["matched"]))
@@ -271,6 +331,8 @@ class CrowdFlowModel:
         if tracker.history:
             extras.update(self._history_keys(K, np.arange(tracker.frames - len(K), tracker.frames), host,
                                              host.get("dwell_total"), tracker.dt))
+        if tracker.crowding:
+            extras.update(self._crowding_keys(K, host, host["crowded_total"], host["peak_total"]))
         return self._measured_flow(host.get("count"), host.get("vsum"), tracker.x_range, tracker.y_range,
                                    tracker.grid_size, min_observations, extras)
 

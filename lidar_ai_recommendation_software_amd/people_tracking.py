@@ -18,6 +18,11 @@ mask per row; ``check_gates`` / ``check_zones`` validate a user's tables on the 
 ``track_history`` (csrc/track_history.hip; DESIGN.md §3 "Track history", §4.13) follows the links forward: per
 detection the age, the hits, the path length and the origin of its track and how long it has been in each zone, per
 frame and zone the stays that ended; ``PeopleTracker(history=True)`` carries that state across ``push`` calls.
+
+``track_crowding`` (csrc/track_crowding.hip; DESIGN.md §3 "Crowding", §4.15) sweeps every frame against itself: per
+person the neighbours within a radius, the nearest one and the spacing, the local density, the variance of the
+velocities around it and their product, the crowd pressure; per frame and venue cell the people above two limits and
+the peaks; ``PeopleTracker(crowding=)`` totals them across ``push`` calls.
 """
 import math
 
@@ -291,6 +296,104 @@ def track_history(people, k, prev, gap=None, zones=None, carry=0, state=None, sl
     return out
 
 
+# ------------------------------------------------------------------ crowding
+# track_crowding's outputs, in order: seven per row, two per frame, two per cell of the venue grid
+CROWDING = ("neighbours", "nearest", "spacing", "density", "movers", "variance", "pressure", "crowded", "peaks",
+            "cell_peak", "cell_crowded")
+DENSITY_LIMIT = 4.0    # people per m^2: the "Critical" edge of CrowdDensityModel.calculate_risk_level
+PRESSURE_LIMIT = 0.02  # 1/s^2: the crowd pressure at which Helbing et al. (2007) report turbulence
+
+
+def crowding_layout(nf, cap, grid):
+    """(name, dtype, shape) of track_crowding's eleven outputs over nf frames; grid: (x0, y0, nx, ny) or None, the
+    two cell arrays then with shape None."""
+    cells = (None, None) if grid is None else (tuple(grid[2:]) + (2,), tuple(grid[2:]))
+    i32, f64 = torch.int32, torch.float64
+    return tuple(zip(CROWDING, (i32, i32, f64, f64, i32, f64, f64, i32, f64, f64, i32),
+                     ((nf, cap),) * 7 + ((nf, 2), (nf, 3)) + cells))
+
+
+def _limit(what, name, v):
+    v = float(v)
+    if not v >= 0.0:
+        raise ValueError(f"{what}: {name} must be >= 0 (inf: never), got {v}")
+    return v
+
+
+def _crowding(people, k, prev, velocity, first, radius, limits, grid, grid_size, accumulate, out, slot):
+    """lidar_track_crowding_f64 over checked tensors: out = the eleven arrays, the last two None without a grid."""
+    x0, y0, nx, ny = grid or (0.0, 0.0, 0, 0)
+    T, cap = people.shape[:2]
+    nat.call("lidar_track_crowding_f64", nat.handle(people.device.index, slot), nat.ptr(people), nat.ptr(k),
+             nat.ptr(prev), nat.ptr(velocity), T, cap, first, radius, *limits, x0, y0, grid_size, nx, ny,
+             1 if accumulate else 0, *(nat.ptr(t) for t in out), nat.stream_ptr())
+
+
+def track_crowding(people, k, prev, velocity, radius, density_limit=DENSITY_LIMIT, pressure_limit=PRESSURE_LIMIT,
+                   x_range=None, y_range=None, grid_size=1.0, first=0, out=None, cells=None, accumulate=False, slot=0):
+    """How tightly packed every tracked person is within its own frame, and how coherently the people around it
+    move (lidar_track_crowding_f64; DESIGN.md §3 "Crowding").  people (T, cap, 2), k (T,), prev (T, cap) int32 and
+    velocity (T, cap, 2) as track_people / track_stream leave them; radius metres; only the frames t >= first are
+    evaluated.  -> CROWDING's eleven, device tensors, nothing synchronised: per row (T - first, cap) neighbours
+    int32 (the valid people within the radius, the row itself not counted; -1 at or past K_t), nearest int32 (the
+    closest valid person of the whole frame, the lowest row on a tie, -1 without one), spacing float64 (the distance
+    to it, inf without one), density float64 ((neighbours + 1) / (pi radius^2), people per m^2), movers int32 (the
+    row and its neighbours that have a measured velocity), variance float64 (the variance of their velocities,
+    (m/s)^2, 0 with fewer than two) and pressure float64 = density * variance (1/s^2, the crowd pressure of Helbing
+    et al., 2007); per frame crowded (T - first, 2) int32 (the people at or above density_limit, at or above
+    pressure_limit) and peaks (T - first, 3) float64 (largest density, largest pressure, smallest spacing); with
+    x_range / y_range per cell of the venue grid (VenueGrid's binning) cell_peak (nx, ny, 2) float64 (largest density
+    and pressure of the people seen in the cell) and cell_crowded (nx, ny) int32 (those at or above density_limit),
+    None without an extent.  The defaults, 4.0 people per m^2 (calculate_risk_level's "Critical") and 0.02 1/s^2 (the
+    level at which Helbing et al. observed turbulence), are starting points for a venue's own limits, not
+    measurements; inf means never.  out: the nine per-row and per-frame arrays preallocated (a None among them is
+    allocated); cells = (cell_peak, cell_crowded) preallocated; accumulate=True goes on from what cells hold (a
+    stream's calls then give one call's bits), otherwise they start from 0.  Every element is written, none of the
+    nine when first == T."""
+    what = "track_crowding"
+    T, cap = _check_people(what, people, k)
+    dev = people.device
+    _check_links(what, people, prev)
+    _check_tensor(what, "velocity", velocity, dev, torch.float64, (T, cap, 2))
+    radius = _positive(what, "radius", radius)
+    limits = _limit(what, "density_limit", density_limit), _limit(what, "pressure_limit", pressure_limit)
+    if (x_range is None) != (y_range is None):
+        raise ValueError(f"{what}: x_range and y_range go together")
+    g = _positive(what, "grid_size", grid_size)
+    grid = None if x_range is None else venue_grid(x_range, y_range, g)  # (x0, y0, nx, ny)
+    first = _integer(what, "first", first, T, "T = ")
+    layout = crowding_layout(T - first, cap, grid)
+    out = _take(what, "out", out, layout[:9], dev, holes=True)
+    if cells is None:
+        if accumulate and grid is not None:
+            raise ValueError(f"{what}: accumulate needs the cells to go on from")
+        with nat.grid_alloc():
+            cells = tuple(None if shape is None else torch.zeros(shape, dtype=dtype, device=dev)
+                          for _, dtype, shape in layout[9:])
+    else:
+        cells = _take(what, "cells", cells, layout[9:], dev)
+        if not accumulate and T == first:  # no native call below: they start from 0 all the same
+            for t in cells:
+                if t is not None:
+                    t.zero_()
+    if T > first:  # an empty tensor has no address to pass
+        _crowding(people, k, prev, velocity, first, radius, limits, grid, g, accumulate, out + cells, slot)
+    return out + cells
+
+
+def _crowding_options(what, crowding):
+    """PeopleTracker's / analyze_sequence's `crowding`: a radius, or a dict with radius and optionally density_limit
+    and pressure_limit -> (radius, (density_limit, pressure_limit))."""
+    opts = dict(crowding) if isinstance(crowding, dict) else {"radius": crowding}
+    extra = set(opts) - {"radius", "density_limit", "pressure_limit"}
+    if extra or "radius" not in opts:
+        raise ValueError(f"{what}: crowding is a radius or a dict with radius, density_limit, pressure_limit, got "
+                         f"{sorted(opts)}")
+    return _positive(what, "crowding radius", opts["radius"]), (
+        _limit(what, "density_limit", opts.get("density_limit", DENSITY_LIMIT)),
+        _limit(what, "pressure_limit", opts.get("pressure_limit", PRESSURE_LIMIT)))
+
+
 class PeopleTracker:
     """A sensor's people tracked batch after batch: ids that last across push() calls, tracks stitched over up
     to max_gap missed frames, and (with a venue extent) the flow cells of everything pushed so far.
@@ -318,10 +421,20 @@ class PeopleTracker:
     (stay and dwell None without zones); dwell_total (Z, 3) int64, with zones: the completed stays of the whole
     stream, their number and summed length added and their largest length maximised across pushes.  However the
     stream is cut, the concatenated last_history and dwell_total are those of one call over the whole stream.
-    Without history the two stay None, and push makes exactly the calls it makes without the keyword."""
+    Without history the two stay None, and push makes exactly the calls it makes without the keyword.
+
+    crowding: a radius in metres, or a dict with radius and optionally density_limit and pressure_limit
+    (track_crowding's defaults).  push then also calls lidar_track_crowding_f64(first = the held frames) after the
+    tracking call (prev and velocity of the new frames are final once that call returns: later passes only look
+    backwards) and keeps the nine per-row and per-frame arrays of the held frames in the window.  last_crowding:
+    track_crowding's first nine outputs for the frames of the last push; crowded_total (2,) int64 and peak_total (3,)
+    float64 (largest density, largest pressure, smallest spacing) cover the whole stream; with an extent cell_peak
+    (nx, ny, 2) and cell_crowded (nx, ny) accumulate on the tracker's venue grid.  However the stream is cut, they are
+    those of one call over the whole stream, bit for bit.  Without crowding they all stay None, and push makes
+    exactly the calls it makes without the keyword."""
 
     def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0, gates=None,
-                 zones=None, history=False):
+                 zones=None, history=False, crowding=None):
         self.dt, self.gate = _positive("PeopleTracker", "dt", dt), _positive("PeopleTracker", "gate", gate)
         self.max_gap = _integer("PeopleTracker", "max_gap", max_gap, MAX_GAP)
         if (x_range is None) != (y_range is None):
@@ -340,18 +453,22 @@ class PeopleTracker:
         self.gate_total = self.zone_total = self.last_events = None
         self.history = bool(history)
         self.last_history = self.dwell_total = None
+        self.crowding = None if crowding is None else _crowding_options("PeopleTracker", crowding)
+        self.last_crowding = self.crowded_total = self.peak_total = self.cell_peak = self.cell_crowded = None
         self._window = None  # name -> tensor: the last frames' arrays, layout()'s rows
 
     def layout(self, T):
         """(name, dtype, shape) of every array held, over T frames: people, k, STATE's five, track_events' arrays with
-        gates / zones (no mask of an absent kind), track_history's state arrays with history=True.  cap: 1 before
-        the first push."""
+        gates / zones (no mask of an absent kind), track_history's state arrays with history=True, track_crowding's
+        nine per-row and per-frame arrays with crowding.  cap: 1 before the first push."""
         cap = self.cap or 1
         rows = (("people", torch.float64, (T, cap, 2)), ("k", torch.int64, (T,))) + state_layout(T, cap)
         if self.events:
             rows += event_layout(T, cap, self.G, self.Z)
         if self.history:
             rows += history_layout(T, cap, self.Z)
+        if self.crowding:
+            rows += crowding_layout(T, cap, None)[:9]
         return tuple(row for row in rows if row[2] is not None)
 
     def held(self):
@@ -378,6 +495,13 @@ class PeopleTracker:
                 self.zone_total = torch.zeros((self.Z, 2), dtype=torch.int64, device=dev)
             if self.history and self.Z:
                 self.dwell_total = torch.zeros((self.Z, 3), dtype=torch.int64, device=dev)
+            if self.crowding:
+                self.crowded_total = torch.zeros(2, dtype=torch.int64, device=dev)
+                self.peak_total = torch.tensor([0.0, 0.0, math.inf], dtype=torch.float64, device=dev)
+                if self.grid is not None:
+                    with nat.grid_alloc():
+                        self.cell_peak = torch.zeros(self.grid[2:] + (2,), dtype=torch.float64, device=dev)
+                        self.cell_crowded = torch.zeros(self.grid[2:], dtype=torch.int32, device=dev)
         if cap != self.cap or dev != self.ntracks.device:
             raise ValueError(f"PeopleTracker.push: cap and device are fixed by the first push ({self.cap}, "
                              f"{self.ntracks.device}), got {cap}, {dev}")
@@ -411,6 +535,16 @@ class PeopleTracker:
                 self.dwell_total[:, :2] += out[5][:, :, :2].sum(dim=0)
                 # the largest of the total and the new frames: no reduction over an empty frame axis at T == 0
                 self.dwell_total[:, 2] = torch.cat([self.dwell_total[None, :, 2], out[5][:, :, 2]]).amax(dim=0)
+        if self.crowding:
+            out = tuple(w[name][C:] for name in CROWDING[:9])
+            if T:
+                _crowding(people, k, prev, w["velocity"], C, self.crowding[0], self.crowding[1], self.grid,
+                          self.grid_size, True, out + (self.cell_peak, self.cell_crowded), self.slot)
+            self.last_crowding = out
+            self.crowded_total += out[7].sum(dim=0, dtype=torch.int64)
+            # the extremes of the total and the new frames: no reduction over an empty frame axis at T == 0
+            self.peak_total[:2] = torch.cat([self.peak_total[None, :2], out[8][:, :2]]).amax(dim=0)
+            self.peak_total[2] = torch.cat([self.peak_total[2:], out[8][:, 2]]).amin()
         self.frames += T
         keep = min(self.max_gap + 1, self.frames)
         self._window = {name: t[C + T - keep:] for name, t in w.items()}
