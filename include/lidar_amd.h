@@ -625,6 +625,49 @@ int lidar_track_history_f64(lidar_handle *h, const double *people, const int64_t
                             int32_t nzones, int32_t *age, int32_t *hits, double *path, double *origin,
                             int32_t *stay, int64_t *dwell, void *stream);
 
+/* Routes (csrc/track_routes.hip; DESIGN.md §3 "Routes", §4.16): where tracked people go next.  Per detection the
+ * first and the last zone its track was seen in, the frames since, the legs it has made and the leg it completes;
+ * per ordered pair of zones the trips, their summed and their longest travel time in frames.  Asynchronous like its
+ * siblings: every pointer a device pointer, no host synchronisation, nothing read back, nothing staged on the host;
+ * scratch (4 bytes per row) from the handle's workspace.  Integers only.
+ *
+ * lidar_track_routes_f64: people, k, prev, gap (or null), frames, cap, K_t, the link guard, carry and the heirs
+ * exactly as lidar_track_history_f64: a row (t, j), j < K_t, is linked iff, with i = prev[t][j] and
+ * g = gap ? gap[t][j] : 1: i >= 0 and 1 <= g <= 8 and g <= t and i < K_(t-g); its source is the row (s, i), s = t - g.
+ * No content of prev / gap makes the call read or write outside the arrays.  Among the rows of frames >= C = carry
+ * that are linked to the same source, the lowest in (t, j) order continues the source's route; every other row of a
+ * frame >= C starts one.  The frames < C hold the given state and are never written.
+ * zones (nzones, 4) rows (x0, x1, y0, y1), 1 <= nzones <= 64, inside() as lidar_track_events_f64;
+ * zone_of(p) = the lowest z with inside(z, p), -1 without one: zones may overlap and the lowest index wins; a NaN
+ * position is in no zone.
+ * Per row of a frame >= C, every element written, all (frames, cap) int32.  c = zone_of(Q), Q the row's own
+ * position; g the frame distance of its link; (F, L, A, N) the source's first_zone, last_zone, away, legs; for a
+ * continuing row with c >= 0, leg = L >= 0 and (L != c or A > 0):
+ *                  starts            continues, c < 0        continues, c >= 0     j >= K_t
+ *   first_zone     c                 F                       F >= 0 ? F : c        -1
+ *   last_zone      c                 L                       c                     -1
+ *   away           c >= 0 ? 0 : -1   L >= 0 ? A + g : -1     0                     -1
+ *   legs           0                 N                       N + leg               0
+ *   leg_from       -1                -1                      leg ? L : -1          -1
+ *   leg_frames     0                 0                       leg ? A + g : 0       0
+ * last_zone: the zone of the track's most recent detection inside any zone; away: the frames since it.  A leg is an
+ * arrival in a zone from another one, or back into the same one after at least one detection outside every zone (a
+ * return, on the diagonal); a link over g > 1 frames with both ends in one zone is one unbroken stay.  leg_frames
+ * runs from the last detection in the zone left to the first in the zone reached.
+ * trips (nzones, nzones, 3) int64, indexed [from][to]: a row with a leg adds 1 to trips[L][c][0] and A + g to
+ * trips[L][c][1] and raises trips[L][c][2] to A + g.  accumulate = 0: trips counts from zero, every element written;
+ * 1: it goes on from what the array holds (non-negative), so a stream's calls give one call's numbers.  Integer
+ * atomics: the same under every schedule.  A carried last_zone >= nzones is no zone of this table: its leg is
+ * written per row as above and adds no trip.
+ *
+ * LIDAR_EINVAL: a null handle, people, k, prev, zones or output; frames < 0 or > 65535, cap < 1, frames * cap >=
+ * 2^31; carry outside 0 .. frames; nzones outside 1 .. 64; accumulate not 0 or 1.  frames == carry returns LIDAR_OK
+ * and writes no row; with accumulate = 0 it still zeroes trips. */
+int lidar_track_routes_f64(lidar_handle *h, const double *people, const int64_t *k, const int32_t *prev,
+                           const int32_t *gap, int64_t frames, int64_t cap, int64_t carry, const double *zones,
+                           int32_t nzones, int32_t *first_zone, int32_t *last_zone, int32_t *away, int32_t *legs,
+                           int32_t *leg_from, int32_t *leg_frames, int64_t *trips, int32_t accumulate, void *stream);
+
 /* Crowding (csrc/track_crowding.hip; DESIGN.md §3 "Crowding", §4.15): per tracked person the number of people
  * within a radius, the nearest one and the distance to it, the local density, and the variance of the velocities
  * around it with their product, the crowd pressure; per frame and per venue cell the counts above two limits and

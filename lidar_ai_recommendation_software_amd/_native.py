@@ -101,6 +101,7 @@ SIGNATURES = {
     "lidar_flow_cells_acc_f64": [P, P, P, P, P, I64, I64, I64, I32, F64, F64, F64, I64, I64, P, P, P],
     "lidar_track_events_f64": [P, P, P, P, P, I64, I64, I64, P, I32, P, I32, P, P, P, P, P, P],
     "lidar_track_history_f64": [P, P, P, P, P, I64, I64, I64, P, I32, P, P, P, P, P, P, P],
+    "lidar_track_routes_f64": [P, P, P, P, P, I64, I64, I64, P, I32, P, P, P, P, P, P, P, I32, P],
     "lidar_track_crowding_f64": [P, P, P, P, P, I64, I64, I64, F64, F64, F64, F64, F64, F64, I64, I64, I32,
                                  P, P, P, P, P, P, P, P, P, P, P, P],
     "lidar_density_batch_f64": [P, P, P, P, I32, P, P, I64, P],

@@ -87,17 +87,23 @@ class CrowdFlowModel:
                 "zone_membership": sliced("zone_in")}
 
     @staticmethod
-    def track_table(track_id, age, hits, path, origin, people, K, frames, dt):
+    def _last_rows(track_id, K):
+        """(ids, r, j): the tracks present among the live rows of track_id (n, cap) with K live rows per frame,
+        ascending, and each one's last row in (t, j) order: the selection track_table and route_table share."""
+        K = np.asarray(K, dtype=np.int64)
+        live = np.arange(track_id.shape[1] if len(K) else 0)[None, :] < K[:, None]
+        r, j = np.nonzero(live) if len(K) else (np.zeros(0, dtype=np.int64),) * 2  # (t, j) ascending
+        ids, back = np.unique(track_id[r, j][::-1], return_index=True)  # the first from the back: the last row
+        return ids, r[::-1][back], j[::-1][back]
+
+    @classmethod
+    def track_table(cls, track_id, age, hits, path, origin, people, K, frames, dt):
         """One entry per track present in the rows read back, from each track's last row in (t, j) order: host
         arrays (n, cap[, 2]) over n frames with K live rows each, frames (n,) their frame numbers -> dict of equally
         long arrays, ascending in track_id: track_id int32, first_frame = last_frame - age and last_frame int64,
         hits int32, path_length, displacement (|last position - origin|) and mean_speed (path_length / (age * dt),
         0.0 where age is 0) float64."""
-        K = np.asarray(K, dtype=np.int64)
-        live = np.arange(track_id.shape[1] if len(K) else 0)[None, :] < K[:, None]
-        r, j = np.nonzero(live) if len(K) else (np.zeros(0, dtype=np.int64),) * 2  # (t, j) ascending
-        ids, back = np.unique(track_id[r, j][::-1], return_index=True)  # the first from the back: the last row
-        r, j = r[::-1][back], j[::-1][back]
+        ids, r, j = cls._last_rows(track_id, K)
         a = age[r, j].astype(np.int64)
         last_frame = np.asarray(frames, dtype=np.int64)[r]
         d = people[r, j] - origin[r, j]
@@ -129,6 +135,36 @@ class CrowdFlowModel:
                         "zone_dwell_mean_s": mean})
         return out
 
+    @classmethod
+    def route_table(cls, track_id, first_zone, last_zone, legs, K):
+        """One entry per track present in the rows read back, from each track's last row in (t, j) order
+        (track_table's selection): host arrays (n, cap) over n frames with K live rows each -> dict of equally long
+        int32 arrays, ascending in track_id: track_id, first_zone, last_zone (-1: never in a zone) and legs."""
+        ids, r, j = cls._last_rows(track_id, K)
+        return {"track_id": ids.astype(np.int32), "first_zone": first_zone[r, j].astype(np.int32),
+                "last_zone": last_zone[r, j].astype(np.int32), "legs": legs[r, j].astype(np.int32)}
+
+    @classmethod
+    def _route_keys(cls, K, host, trips, dt):
+        """The routes keys of analyze_sequence / analyze_stream from host copies: in `host`, under their names,
+        track_id and track_routes' six arrays over the frames K; trips (Z, Z, 3): the whole stream's."""
+        rows = range(len(K))
+        count, total = trips[:, :, 0].astype(np.int64), trips[:, :, 1].astype(np.int64)
+        with np.errstate(all="ignore"):
+            mean = np.where(count > 0, np.float64(dt) * total / count, np.nan)
+        table = cls.route_table(host["track_id"], host["first_zone"], host["last_zone"], host["legs"], K)
+        Z = trips.shape[0]
+        od = np.zeros((Z, Z), dtype=np.int64)
+        first, last = table["first_zone"], table["last_zone"]
+        seen = (first >= 0) & (first < Z) & (last >= 0) & (last < Z)  # a track that was never in a zone is left out
+        np.add.at(od, (first[seen], last[seen]), 1)
+        out = {key: [host[name][t, :K[t]] for t in rows] for key, name in (
+            ("first_zones", "first_zone"), ("last_zones", "last_zone"), ("away", "away"), ("legs", "legs"),
+            ("leg_from", "leg_from"), ("leg_frames", "leg_frames"))}
+        out.update({"zone_trips": count, "zone_trip_frames": total, "zone_trip_max": trips[:, :, 2].astype(np.int64),
+                    "zone_trip_mean_s": mean, "route_table": table, "od_matrix": od})
+        return out
+
     RISK_LEVELS = ("Low", "Moderate", "High", "Critical")  # calculate_risk_level's classes, risk_levels' columns
 
     @classmethod
@@ -157,7 +193,7 @@ class CrowdFlowModel:
 
     def analyze_sequence(self, people, k=None, *, dt, x_range, y_range, gate=None, max_speed=3.0, grid_size=1.0,
                          min_observations=1, max_gap=0, gates=None, zones=None, history=False, crowding=None,
-                         density_limit=4.0, pressure_limit=0.02):
+                         density_limit=4.0, pressure_limit=0.02, routes=False):
         """Measured flow of T consecutive frames (no reference counterpart: its flow field is simulated).
 
         people: the device tensor (T, cap, 2) float64 with k (T,) int64 (``pointnet2.class_people``'s outputs),
@@ -209,7 +245,18 @@ class CrowdFlowModel:
         crowded_cells (nx, ny) int32 on the venue grid; risk_levels (T, 4) int64, the people of each frame in
         ``CrowdDensityModel.calculate_risk_level``'s classes Low / Moderate / High / Critical of their local
         density.  density_limit 4.0 people per m^2 is that function's "Critical" edge and pressure_limit 0.02 1/s^2
-        the turbulence level Helbing et al. report: defaults to override per venue, not measurements."""
+        the turbulence level Helbing et al. report: defaults to override per venue, not measurements.
+
+        routes=True (needs zones) adds where people go next (``people_tracking.track_routes``, DESIGN.md §3
+        "Routes"), in the same read-back; a position belongs to the lowest zone that holds it.  zone_trips,
+        zone_trip_frames and zone_trip_max (Z, Z) int64, indexed [from][to]: the legs of the sequence (an arrival in
+        a zone from another one, or a return into the same one after a detection outside every zone, on the
+        diagonal), their summed and their longest length in frames; zone_trip_mean_s (Z, Z) float64 =
+        dt * frames / count, NaN without a trip; first_zones, last_zones, away, legs, leg_from and leg_frames: per
+        frame (K_t,) int32 (the first zone of the row's track and the zone it was last seen in, -1 for none; the
+        frames since; the legs so far; on a row that completes a leg the zone left and the frames it took, -1 and 0
+        otherwise); route_table, ``route_table``'s dict with one entry per track of the sequence; od_matrix (Z, Z)
+        int64, route_table's tracks counted by [first_zone][last_zone], those never in a zone left out."""
         import torch
         from . import people_tracking as pt
 
@@ -229,6 +276,8 @@ class CrowdFlowModel:
         max_gap = pt._integer(what, "max_gap", max_gap, pt.MAX_GAP)
         gates = None if gates is None else pt.check_gates(gates)
         zones = None if zones is None else pt.check_zones(zones)
+        if routes and zones is None:
+            raise ValueError("analyze_sequence: routes need zones")
         if crowding is not None:
             crowding = pt._crowding_options(what, {"radius": crowding, "density_limit": density_limit,
                                                    "pressure_limit": pressure_limit})
@@ -264,6 +313,8 @@ class CrowdFlowModel:
             named["people"] = people
             named.update(zip([name for name, _, _ in pt.HISTORY] + ["stay", "dwell"],
                              pt.track_history(people, k, prev, gap, tables[1])))
+        if routes:
+            named.update(zip(pt.ROUTES + ("trips",), pt.track_routes(people, k, prev, gap, tables[1])))
         if crowding is not None:
             named["people"] = people
             named.update(zip(pt.CROWDING, pt.track_crowding(people, k, prev, velocity, crowding[0], *crowding[1],
@@ -279,6 +330,8 @@ class CrowdFlowModel:
             total = None if dwell is None else np.concatenate(
                 [dwell[:, :, :2].sum(axis=0), dwell[:, :, 2].max(axis=0, initial=0)[:, None]], axis=1)
             extras.update(self._history_keys(K, np.arange(len(K)), host, total, dt))
+        if routes:
+            extras.update(self._route_keys(K, host, host["trips"], dt))
         if crowding is not None:
             peaks = host["peaks"]
             extras.update(self._crowding_keys(K, host, host["crowded"].sum(axis=0), np.array(
@@ -297,7 +350,10 @@ class CrowdFlowModel:
         held frames, track_table the tracks present in them (frames counted from the first pushed frame), and the
         zone_dwell keys total the whole stream.  A tracker built with crowding adds ``analyze_sequence``'s crowding
         keys, in the same read-back: the per-frame lists, crowded_series, peak_series and risk_levels cover the held
-        frames; crowded_total, peak_density, peak_pressure, min_spacing and the two cell maps the whole stream."""
+        frames; crowded_total, peak_density, peak_pressure, min_spacing and the two cell maps the whole stream.  A
+        tracker built with routes=True adds ``analyze_sequence``'s routes keys, in the same read-back: the per-frame
+        lists cover the held frames, route_table and od_matrix the tracks present in them, and the zone_trip keys
+        total the whole stream."""
         import torch
 
         if int(min_observations) != min_observations or min_observations < 1:
@@ -310,6 +366,8 @@ class CrowdFlowModel:
                         zone_total=np.zeros((tracker.Z, 2), dtype=np.int64))
             if tracker.history and tracker.Z:
                 host["dwell_total"] = np.zeros((tracker.Z, 3), dtype=np.int64)
+            if tracker.routes:
+                host["trips_total"] = np.zeros((tracker.Z, tracker.Z, 3), dtype=np.int64)
             if tracker.crowding:
                 host.update(crowded_total=np.zeros(2, dtype=np.int64), peak_total=np.array([0.0, 0.0, np.inf]),
                             cell_peak=np.zeros(tracker.grid[2:] + (2,)),
@@ -321,6 +379,7 @@ class CrowdFlowModel:
             host = _read_back({**held, "ntracks": tracker.ntracks, "matched": tracker.matched, "count": tracker.count,
                                "vsum": tracker.vsum, "gate_total": tracker.gate_total,
                                "zone_total": tracker.zone_total, "dwell_total": tracker.dwell_total,
+                               "trips_total": tracker.trips_total,
                                "crowded_total": tracker.crowded_total, "peak_total": tracker.peak_total,
                                "cell_peak": tracker.cell_peak, "cell_crowded": tracker.cell_crowded},
                               tracker.ntracks.device)  # the one read-back
@@ -331,6 +390,8 @@ class CrowdFlowModel:
         if tracker.history:
             extras.update(self._history_keys(K, np.arange(tracker.frames - len(K), tracker.frames), host,
                                              host.get("dwell_total"), tracker.dt))
+        if tracker.routes:
+            extras.update(self._route_keys(K, host, host["trips_total"], tracker.dt))
         if tracker.crowding:
             extras.update(self._crowding_keys(K, host, host["crowded_total"], host["peak_total"]))
         return self._measured_flow(host.get("count"), host.get("vsum"), tracker.x_range, tracker.y_range,

@@ -24,9 +24,10 @@
 //   integer atomics leave them the same under every schedule.
 //
 // Kernels, three launches, no workgroup waiting for another:
-//   init_kernel    next[row] = kNone over the rows a claim can name, dwell = 0.
-//   claim_kernel   a thread per row of the frames >= C; a linked row takes atomicMin(next[source], its own index):
-//                  the minimum is the heir rule.
+//   init_kernel    (track_chain.hpp, shared with track_routes.hip) next[row] = kNone over the rows a claim can name,
+//                  dwell = 0.
+//   claim_kernel   (track_chain.hpp) a thread per row of the frames >= C; a linked row takes atomicMin(next[source],
+//                  its own index): the minimum is the heir rule.
 //   walk_kernel (Z = 0), walk_zones_kernel (Z > 0): a walker per row of the frames >= C.  A row at or past K_t gets
 //                  the defaults.  A live row that is the heir of a row of a frame >= C leaves: the walker that comes
 //                  through its source writes it.  Every other live row is a walk start (the start of a history, or
@@ -42,40 +43,15 @@
 //                  per zone and step: 3 times slower at 8 zones, 10 to 20 times at 64)
 #include <cmath>
 
-#include "track_links.hpp"
+#include "track_chain.hpp"
 
 namespace {
 
 using namespace lidar::tier_r;
 using namespace lidar::track;
 
-constexpr int kB = 256;              // threads per workgroup
 constexpr int kWaves = kB / 64;
-constexpr int32_t kNone = 0x7fffffff;  // above every row index: frames * cap < 2^31
 static_assert(kMaxTab <= 64, "a zone per lane");
-
-__global__ __launch_bounds__(kB) void init_kernel(int32_t *__restrict__ next, int64_t nn, int64_t *__restrict__ dwell,
-                                                  int64_t nd)
-{
-    for (int64_t e = (int64_t)blockIdx.x * kB + threadIdx.x; e < nn + nd; e += (int64_t)gridDim.x * kB) {
-        if (e < nn) next[e] = kNone;
-        else dwell[e - nn] = 0;
-    }
-}
-
-// blockIdx.y = t - carry; blockIdx.x and gridDim.x stride over the frame's row tiles.
-__global__ __launch_bounds__(kB) void claim_kernel(const int64_t *__restrict__ k, const int32_t *__restrict__ prev,
-                                                   const int32_t *__restrict__ gap, int64_t cap, int64_t carry,
-                                                   int32_t *__restrict__ next)
-{
-    const int64_t t = carry + blockIdx.y, K = clamp_k(k, t, cap);
-    for (int64_t j = (int64_t)blockIdx.x * kB + threadIdx.x; j < K; j += (int64_t)gridDim.x * kB) {
-        const int64_t e = t * cap + j;
-        int64_t g;
-        const int64_t a = source_of(k, prev, gap, cap, t, e, g);
-        if (a >= 0) atomicMin(&next[a], (int32_t)e);
-    }
-}
 
 // The history state a walker carries from one row to the next.
 struct Hist {
@@ -259,8 +235,7 @@ LIDAR_EXPORT int lidar_track_history_f64(lidar_handle *h, const double *people, 
     int32_t *next = static_cast<int32_t *>(lidar::workspace(h, (uint64_t)(frames * cap) * sizeof(int32_t)));
     if (!next) return LIDAR_ENOMEM;
     const int64_t nd = nf * nzones * 3;
-    const unsigned tiles = (unsigned)std::min<int64_t>((cap + kB - 1) / kB, 4096);
-    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nn + nd + kB - 1) / kB, 4096));
+    const unsigned tiles = row_tiles(cap), blocks = init_blocks(nn + nd);
 
     lidar::Span sp(h, "track_history", s);
     hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(kB), 0, s, next + lo, nn, dwell, nd);

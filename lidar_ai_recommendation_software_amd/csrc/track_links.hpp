@@ -1,5 +1,6 @@
-// track_links.hpp — what track.hip, track_events.hip and track_history.hip share: a frame's live row count, what a
-// valid link (prev, gap) is, the zone predicate and the range checks of a (frames, cap) call.  No kernels here.
+// track_links.hpp — what track.hip, track_events.hip, track_history.hip and track_routes.hip share: a frame's live row
+// count, what a valid link (prev, gap) is, the zone predicate and the range checks of a (frames, cap) call.  No kernels
+// here (the two that turn links into chains are in track_chain.hpp).
 #pragma once
 #include "tier_r.hpp"
 

@@ -23,6 +23,11 @@ frame and zone the stays that ended; ``PeopleTracker(history=True)`` carries tha
 person the neighbours within a radius, the nearest one and the spacing, the local density, the variance of the
 velocities around it and their product, the crowd pressure; per frame and venue cell the people above two limits and
 the peaks; ``PeopleTracker(crowding=)`` totals them across ``push`` calls.
+
+``track_routes`` (csrc/track_routes.hip; DESIGN.md §3 "Routes", §4.16) joins a track's visit to one zone with its
+visit to the next: per detection the first and the last zone of its track, the frames since, its legs and the leg it
+completes, per pair of zones the trips and their travel times; ``PeopleTracker(routes=True)`` carries that state and
+totals the trips across ``push`` calls.
 """
 import math
 
@@ -296,6 +301,53 @@ def track_history(people, k, prev, gap=None, zones=None, carry=0, state=None, sl
     return out
 
 
+# ------------------------------------------------------------------ routes
+ROUTES = ("first_zone", "last_zone", "away", "legs", "leg_from", "leg_frames")  # track_routes' state arrays, in order
+
+
+def routes_layout(T, cap, Z):
+    """(name, dtype, shape) of track_routes' outputs over T frames: ROUTES' six (T, cap) int32, then trips (Z, Z, 3)
+    int64."""
+    return tuple((name, torch.int32, (T, cap)) for name in ROUTES) + (("trips", torch.int64, (Z, Z, 3)),)
+
+
+def track_routes(people, k, prev, gap=None, zones=None, carry=0, state=None, trips=None, accumulate=False, slot=0):
+    """Where every tracked person goes next: zone-to-zone trips and their travel times from the links (prev, gap)
+    track_people / track_stream left on the device (lidar_track_routes_f64; DESIGN.md §3 "Routes").  people
+    (T, cap, 2), k (T,), prev (T, cap) int32; gap (T, cap) int32, or None for track_people's prev (every link spans
+    one frame); zones (Z, 4) float64 device tensor, 1 .. 64 rows as track_events takes it, needed: a position belongs
+    to the lowest zone that holds it, so the table is ordered by priority; the first `carry` (0 .. T) frames' route
+    state is given in `state` = ROUTES' six arrays, each (T, cap) int32; the call fills the other frames in place.
+    Without a state (carry 0) they are allocated.  -> (first_zone, last_zone, away, legs, leg_from, leg_frames, trips),
+    device tensors, nothing synchronised: per row the first zone the track was seen in and the zone of its most
+    recent detection inside any zone (-1: none yet), the frames since that detection, the legs made so far, and, on
+    the row that completes a leg (an arrival from another zone, or back into the same one after a detection outside
+    every zone), the zone left and the frames from the last detection there to this one (-1 and 0 otherwise); trips
+    (Z, Z, 3) int64 indexed [from][to]: the legs, their summed and their longest length in frames.  trips: the array
+    to use; accumulate=True goes on from what it holds (a stream's calls then give one call's numbers), otherwise it
+    counts from zero.  T == carry: no row is written."""
+    what = "track_routes"
+    T, cap = _check_people(what, people, k)
+    dev = people.device
+    _check_links(what, people, prev, gap)
+    Z = _check_device_table(what, "zones", zones, dev)
+    if not Z:
+        raise ValueError(f"{what}: needs zones")
+    carry = _integer(what, "carry", carry, T, "T = ")
+    layout = routes_layout(T, cap, Z)
+    state = _take(what, "state", state, layout[:6], dev, carry=carry)
+    if trips is None and accumulate:
+        raise ValueError(f"{what}: accumulate needs the trips to go on from")
+    trips, = _take(what, "trips", None if trips is None else (trips,), layout[6:], dev)
+    if T > carry:  # an empty tensor has no address to pass
+        nat.call("lidar_track_routes_f64", nat.handle(dev.index, slot), nat.ptr(people), nat.ptr(k), nat.ptr(prev),
+                 nat.ptr(gap), T, cap, carry, nat.ptr(zones), Z, *(nat.ptr(t) for t in state), nat.ptr(trips),
+                 1 if accumulate else 0, nat.stream_ptr())
+    elif not accumulate:  # no native call: the trips count from zero all the same
+        trips.zero_()
+    return state + (trips,)
+
+
 # ------------------------------------------------------------------ crowding (DESIGN.md §4.15)
 # track_crowding's outputs, in order: seven per row, two per frame, two per cell of the venue grid
 CROWDING = ("neighbours", "nearest", "spacing", "density", "movers", "variance", "pressure", "crowded", "peaks",
@@ -431,10 +483,18 @@ class PeopleTracker:
     float64 (largest density, largest pressure, smallest spacing) cover the whole stream; with an extent cell_peak
     (nx, ny, 2) and cell_crowded (nx, ny) accumulate on the tracker's venue grid.  However the stream is cut, they are
     those of one call over the whole stream, bit for bit.  Without crowding they all stay None, and push makes
-    exactly the calls it makes without the keyword."""
+    exactly the calls it makes without the keyword.
+
+    routes=True (needs zones): push also calls lidar_track_routes_f64(carry = the held frames, accumulate = 1) after
+    the tracking call, with the zones table, and keeps the six route arrays of the held frames beside history's.
+    last_routes: ROUTES' six arrays for the frames of the last push; trips_total (Z, Z, 3) int64, indexed [from][to]:
+    the legs of the whole stream, their summed and their longest length in frames, accumulated on the device by the
+    call itself.  However the stream is cut, the concatenated last_routes and trips_total are those of one call over
+    the whole stream.  Without routes the two stay None, and push makes exactly the calls it makes without the
+    keyword."""
 
     def __init__(self, dt, gate, max_gap=0, x_range=None, y_range=None, grid_size=1.0, slot=0, gates=None,
-                 zones=None, history=False, crowding=None):
+                 zones=None, history=False, crowding=None, routes=False):
         self.dt, self.gate = _positive("PeopleTracker", "dt", dt), _positive("PeopleTracker", "gate", gate)
         self.max_gap = _integer("PeopleTracker", "max_gap", max_gap, MAX_GAP)
         if (x_range is None) != (y_range is None):
@@ -455,18 +515,24 @@ class PeopleTracker:
         self.last_history = self.dwell_total = None
         self.crowding = None if crowding is None else _crowding_options("PeopleTracker", crowding)
         self.last_crowding = self.crowded_total = self.peak_total = self.cell_peak = self.cell_crowded = None
+        self.routes = bool(routes)
+        if self.routes and not self.Z:
+            raise ValueError("PeopleTracker: routes need zones")
+        self.last_routes = self.trips_total = None
         self._window = None  # name -> tensor: the last frames' arrays, layout()'s rows
 
     def layout(self, T):
         """(name, dtype, shape) of every array held, over T frames: people, k, STATE's five, track_events' arrays with
-        gates / zones (no mask of an absent kind), track_history's state arrays with history=True, track_crowding's
-        nine per-row and per-frame arrays with crowding.  cap: 1 before the first push."""
+        gates / zones (no mask of an absent kind), track_history's state arrays with history=True, track_routes' six
+        with routes=True, track_crowding's nine per-row and per-frame arrays with crowding.  cap: 1 before the first push."""
         cap = self.cap or 1
         rows = (("people", torch.float64, (T, cap, 2)), ("k", torch.int64, (T,))) + state_layout(T, cap)
         if self.events:
             rows += event_layout(T, cap, self.G, self.Z)
         if self.history:
             rows += history_layout(T, cap, self.Z)
+        if self.routes:
+            rows += routes_layout(T, cap, self.Z)[:6]
         if self.crowding:
             rows += crowding_layout(T, cap, None)[:9]
         return tuple(row for row in rows if row[2] is not None)
@@ -495,6 +561,8 @@ class PeopleTracker:
                 self.zone_total = torch.zeros((self.Z, 2), dtype=torch.int64, device=dev)
             if self.history and self.Z:
                 self.dwell_total = torch.zeros((self.Z, 3), dtype=torch.int64, device=dev)
+            if self.routes:
+                self.trips_total = torch.zeros((self.Z, self.Z, 3), dtype=torch.int64, device=dev)
             if self.crowding:
                 self.crowded_total = torch.zeros(2, dtype=torch.int64, device=dev)
                 self.peak_total = torch.tensor([0.0, 0.0, math.inf], dtype=torch.float64, device=dev)
@@ -521,7 +589,7 @@ class PeopleTracker:
             if self.grid is not None:
                 _flow_cells_acc(people, k, prev, w["velocity"], C, 1, self.grid, self.grid_size, self.count, self.vsum,
                                 self.slot)
-        # track_events and track_history make no native call either when no frame follows the held ones
+        # track_events, track_history and track_routes make no native call either when no frame follows the held ones
         if self.events:
             out = tuple(w[name][C:] if name in w else None for name in EVENTS)
             self.last_events = track_events(people, k, prev, gap, *self._tables, first=C, out=out, slot=self.slot)
@@ -535,6 +603,10 @@ class PeopleTracker:
                 self.dwell_total[:, :2] += out[5][:, :, :2].sum(dim=0)
                 # the largest of the total and the new frames: no reduction over an empty frame axis at T == 0
                 self.dwell_total[:, 2] = torch.cat([self.dwell_total[None, :, 2], out[5][:, :, 2]]).amax(dim=0)
+        if self.routes:  # the trips go on in trips_total: no torch add per push
+            out = track_routes(people, k, prev, gap, self._tables[1], C, tuple(w[name] for name in ROUTES),
+                               self.trips_total, True, self.slot)
+            self.last_routes = tuple(t[C:] for t in out[:6])
         if self.crowding:
             out = tuple(w[name][C:] for name in CROWDING[:9])
             if T:
