@@ -120,6 +120,10 @@ def frames_for(kind, b, n, seed):
     ("uniform", 2, 1, 4), ("uniform", 1, 37, 60), ("uniform", 1, 64, 64),
     ("offset", 2, 20000, 700), ("flat", 2, 9000, 500), ("nonfinite", 2, 3000, 300), ("uniform", 2, 4097, 300),
     ("grid", 1, 4096, 4096),
+    # the launch table's thresholds (bucket slots per lane): 1 -> 2 at 512 threads, 1 -> 2 at 1 024, 4 -> 8 at
+    # 512 and 2 -> 4 at 1 024, and the last one-point-per-lane frame
+    ("uniform", 1, 32768, 48), ("uniform", 1, 32769, 48), ("uniform", 1, 65537, 48), ("uniform", 1, 131073, 48),
+    ("uniform", 1, 262144, 48),
 ])
 @pytest.mark.parametrize("threads", [0, 512])
 def test_fps_bit_exact(cuda, kind, b, n, m, threads):
@@ -127,10 +131,6 @@ def test_fps_bit_exact(cuda, kind, b, n, m, threads):
     coordinates against the C oracle (incl. far-offset, zero-width, non-finite and lattice frames, m up to
     n)."""
     x = frames_for(kind, b, n, 11)
-    if threads and (n + 63) // 64 > 8 * threads:  # 8 buckets per lane at most
-        with pytest.raises(LidarError, match="too many buckets"):
-            pn.farthest_point_sample(torch.from_numpy(x).to(cuda), m, threads=threads)
-        return
     idx, nx = pn.farthest_point_sample(torch.from_numpy(x).to(cuda), m, return_xyz=True, threads=threads)
     want = tier_n.fps(x, m)
     got = idx.cpu().numpy()
@@ -138,7 +138,9 @@ def test_fps_bit_exact(cuda, kind, b, n, m, threads):
     assert np.array_equal(nx.cpu().numpy(), np.take_along_axis(x, want[..., None].astype(np.int64), 1))
 
 
-@pytest.mark.parametrize("n,m", [(300000, 2048), (600000, 700), (1100000, 300), (2200000, 96), (4194304, 40)])
+@pytest.mark.parametrize("n,m", [(300000, 2048), (600000, 700), (1100000, 300), (2200000, 96), (4194304, 40),
+                                 # the launch table's thresholds: the first PPL 2 frame, PPL 2 -> 4, 4 -> 8, the last PPL 8
+                                 (262145, 24), (524288, 24), (524289, 24), (1048577, 24), (2097152, 24)])
 def test_fps_large_frames_bit_exact(cuda, n, m):
     """Frames above 262 144 points (8 bucket slots per lane at 512 threads) take buckets of 64 x PPL
     points (PPL 2 / 4 / 8 / 16 here; 16 — the most registers, P[K][16] — from 2 097 153 points up to the

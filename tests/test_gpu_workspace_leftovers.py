@@ -26,7 +26,7 @@ The carve-ups, one sentence per sub-buffer: who writes it before whom.
 
 FPS (fps.hip, per frame b at ``ws + b * stride``, stride = align64(5 * npad) floats)
   * ``p`` float4[npad]: fps_prologue scatters all n points into [0, n) by Morton cell and writes the sentinel rows
-    [n, npad) before its closing barrier; the bbox pass and the step loop read after that barrier.
+    [n, npad) before its closing barrier; bucket_boxes and the step loop read after that barrier.
   * ``d`` float[npad]: fps_prologue writes inf over [0, n) and -1 over [n, npad) at the same place; the step loop
     reads and updates it afterwards.  The stride's alignment gap is never touched.
 Ball query through the handle (ball_query.hip, per frame ``BqGrid | tab[kTab + 64] | sorted float4[n]``)

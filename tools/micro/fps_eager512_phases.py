@@ -1,11 +1,12 @@
-"""Where an FPS step's time goes: the DIAG build of fps_bucket_kernel<1024, 1> (lidar_diag_fps_eager512_phases)
+"""Where an FPS step's time goes: the DIAG build of fps_bucket_kernel<512, BPL> (lidar_diag_fps_eager512_phases;
+BPL 1 up to 32 768 points, 2 up to 65 536)
 stamps the shader clock around each phase of every step, per wave.  Prints, per step averaged over
 frames and waves: [0] bucket tests + active-bucket updates (loads, distances, DPP reductions),
-[1] wave argmax + LDS publish, [2] barrier wait, [3] 16-way merge, plus active-bucket batches per
+[1] wave argmax + LDS publish, [2] barrier wait, [3] 8-way merge, plus active-bucket batches per
 wave-step, and the same for the first / last 256 steps.
 
 usage (the diagnostic library, `make -C lidar_ai_recommendation_software_amd/csrc diag`):
-LIDAR_AMD_LIB=lidar_ai_recommendation_software_amd/liblidar_amd_diag.so python tools/micro/fps_phases.py [B] [N] [M]"""
+LIDAR_AMD_LIB=lidar_ai_recommendation_software_amd/liblidar_amd_diag.so python tools/micro/fps_eager512_phases.py [B] [N] [M]"""
 import ctypes
 import os
 import sys

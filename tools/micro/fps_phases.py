@@ -1,5 +1,5 @@
-"""Where an FPS step's time goes: the DIAG build of fps_bucket_kernel<1024, 1> (lidar_diag_fps_phases)
-stamps the shader clock around each phase of every step, per wave.  Prints, per step averaged over
+"""Where an FPS step's time goes: the DIAG build of fps_bucket_kernel<1024, 1> (lidar_diag_fps_phases,
+N <= 65 536) stamps the shader clock around each phase of every step, per wave.  Prints, per step averaged over
 frames and waves: [0] bucket tests + active-bucket updates (loads, distances, DPP reductions),
 [1] wave argmax + LDS publish, [2] barrier wait, [3] 16-way merge, plus active-bucket batches per
 wave-step, and the same for the first / last 256 steps.

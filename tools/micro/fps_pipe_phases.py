@@ -1,6 +1,7 @@
 """The SA1 FPS step phases INSIDE the bench's pipeline, beside the same kernel alone.
 
 The diagnostic library's lidar_diag_fps_record makes every SA1 FPS launch of 512 threads (no prefix_ok)
+of at most 65 536 points
 take the DIAG instantiation of fps_bucket_kernel<512, BPL> and append its per-(frame, wave) phase totals:
 [0] bucket tests + active-bucket updates, [1] wave argmax + LDS publish, [2] barrier wait, [3] merge,
 [4] active-bucket batches, [5] steps.  The pipeline is bench.py's (SSG, 32 x 65 536-point batches,
